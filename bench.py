@@ -1,8 +1,13 @@
 """Headline benchmark: images/sec of one ViT-B/16 CLIP+MAE training step
 (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...); --dump-outputs
+DIR also writes what the last timed step computed (dump_outputs below). Every
+other leg -- the extra fields listed further down -- runs only with --full.
 
 Workload per GPU = BASELINE.json configs[2] / configs[3]: ViT-B/16 @224, 256
 images per GPU, MAE mask 0.75 + 8-layer 512-d decoder, 6-layer frozen
@@ -12,13 +17,14 @@ step, bf16 MFMA with fp32 master weights. Synthetic inputs already resident in
 HBM (uint8 pixels ImageNet-normalised, input_ids randint(5,300)).
 Weak scaling: per-GPU batch fixed, value = global images / max-over-ranks time.
 
-Extra fields: "roofline" (the launch shape with the largest total time per
+Extra fields (--full only): "roofline" (the launch shape with the largest total time per
 step -- forward / dgrad GEMMs and the grouped weight-gradient launches of the
 main stream -- timed live during the timed steps on its stream),
 "roofline_fwd_dgrad" (the same for the largest forward / dgrad GEMM shape),
 "cpu_baseline" (the CPU oracle of /oracle on a bounded sample, rank 0 at N=1
 only), "loss_delta_vs_ref" (C0 fp32 parity), "u8_input_pipeline" (N=1: the
-step with the uint8 pixel H2D copy inside the timed region, main.py:55).
+step with the uint8 pixel H2D copy inside the timed region, main.py:55),
+"sync_loss_leg" (the same steps with a blocking loss read after each).
 """
 from __future__ import annotations
 
@@ -441,6 +447,51 @@ def u8_leg(model, opt, args, size, device, use_graph):
                                      "before the next is queued: main.py:55 and :64 together"}}
 
 
+DUMP_SAMPLE = 8192   # elements kept of each parameter / gradient tensor by --dump-outputs
+
+
+def dump_outputs(path, model, loss, losses):
+    """--dump-outputs: what the last timed step handed its caller, as
+    <path>/<name>.npy (float64 scalars, float32 arrays; under 8 MB at C2):
+    loss / loss_clip / loss_mae (the step's loss and its two terms), losses
+    (every timed step's loss as the loop read it), mae_mask / mae_ids_shuffle
+    (the step's MAE masking), and params_sample / grads_sample: of every
+    trainable parameter after the step's AdamW update, and of its gradient, the
+    whole tensor up to DUMP_SAMPLE elements, else DUMP_SAMPLE elements at fixed
+    seeded positions, concatenated in named_parameters() order (a parameter
+    without a gradient contributes zeros)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+
+    def save(name, a, dtype):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(np.asarray(a, dtype=dtype)))
+
+    save("loss", [loss.item()], np.float64)
+    save("losses", losses, np.float64)
+    for k, v in model.last_losses.items():
+        save("loss_" + k, [v.item()], np.float64)
+    if model.mae_decoder is not None:
+        ids_shuffle, _, mask = model.last_mask
+        save("mae_mask", mask.float().cpu().numpy(), np.float32)
+        save("mae_ids_shuffle", ids_shuffle.float().cpu().numpy(), np.float32)
+    g = torch.Generator(device="cpu").manual_seed(4321)
+    ps, gs = [], []
+    for _, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        n = p.numel()
+        flat = p.detach().reshape(-1)
+        grad = p.grad.detach().reshape(-1) if p.grad is not None else torch.zeros_like(flat)
+        if n > DUMP_SAMPLE:
+            idx = torch.randint(n, (DUMP_SAMPLE,), generator=g).to(flat.device)
+            flat, grad = flat[idx], grad[idx]
+        ps.append(flat.float())
+        gs.append(grad.float())
+    save("params_sample", torch.cat(ps).cpu().numpy(), np.float32)
+    save("grads_sample", torch.cat(gs).cpu().numpy(), np.float32)
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N ranks through
     torch.distributed.run (one process per GPU) and relay rank 0's JSON line.
@@ -470,6 +521,14 @@ def main():
                     help="GEMM operand precision (fp8: OCP e4m3 forward and dgrad GEMMs of the encoder and decoder stacks "
                          "(config.fp8_grad_format), e8m0 per-32 blocks / per-row scales on the activations, "
                          "per-channel on the weights)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg of the line: the in-step launch timer and its roofline "
+                         "objects, the sync-loss leg, the uint8 input-pipeline leg, the parity / train-curve "
+                         "checks against the CPU oracle and the CPU baseline (each can be dropped again by "
+                         "its --no-... option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy "
+                         "(dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--no-kernel-timer", action="store_true")
@@ -487,6 +546,13 @@ def main():
     ap.add_argument("--no-u8-leg", action="store_true",
                     help="skip the extra input-pipeline measurement (uint8 pixels H2D + fused Normalize in the step)")
     args = ap.parse_args()
+    # a plain run does only what the headline figure needs; --full adds the
+    # other legs (--gemm-table asks for the launch timer by itself)
+    run_timer = (args.full or args.gemm_table) and not args.no_kernel_timer
+    run_sync_leg = args.full and not args.sync_loss
+    run_u8_leg = args.full and not args.no_u8_leg
+    run_parity = args.full and not args.no_parity
+    run_cpu_baseline = args.full and not args.no_cpu_baseline
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
@@ -523,6 +589,9 @@ def main():
     args.mask_ratio = mcfg["mask_ratio"]
     img_flops = cfg["flops"] if args.mask_ratio == cfg["model"]["mask_ratio"] else None
     size = mcfg["size"]
+    # the random-init weights are an input of the run like the batch: the same
+    # on every run (and rank), so that two runs compute the same steps
+    torch.manual_seed(20240)
     model = build_model(dict(mcfg, text_layers=6, decoder_embed_dim=512, decoder_depth=8,
                              decoder_num_heads=16, precision=args.precision,
                              side_stream=not args.no_side_stream,
@@ -533,7 +602,7 @@ def main():
     batch = synthetic_batch(args.batch, size, 25, 1000 + rank, device)
 
     timer = KernelTimer()
-    if not args.no_kernel_timer:
+    if run_timer:
         K.LAUNCH_HOOK = timer.hook
 
     # one HIP graph per step (mae_clip_amd.graph): steps 1-2 eager, step 3
@@ -593,10 +662,13 @@ def main():
     assert len(losses) == args.steps and all(math.isfinite(v) for v in losses), losses
     timer.harvest()
     timer.active = False
+    if args.dump_outputs and rank == 0:
+        # before any other leg steps the model again
+        dump_outputs(args.dump_outputs, model, loss, losses)
     # the drop-in loop as main.py:64 runs it: each step's loss read (blocking)
     # before the next step is queued; reported beside the headline, not as value
     sync_el = None
-    if not args.sync_loss:
+    if run_sync_leg:
         if use_dp:
             dist.barrier()
         torch.cuda.synchronize()
@@ -616,16 +688,16 @@ def main():
     value = global_batch * args.steps / elapsed
     ms = elapsed / args.steps * 1000.0
 
-    if rank == 0 and args.gemm_table and not args.no_kernel_timer:
+    if rank == 0 and args.gemm_table and run_timer:
         timer.table(args.steps, sys.stderr)
     u8 = None
-    if not args.no_u8_leg and world == 1:
+    if run_u8_leg and world == 1:
         u8 = u8_leg(model, opt, args, size, device, use_graph)
     if rank == 0:
         roof = roof2 = None
         # the dominant launch among those that run alone (a co-running
         # micro-batch chain would make its span more than its own duration)
-        best = (timer.summary(is_alone) or timer.summary()) if not args.no_kernel_timer else None
+        best = (timer.summary(is_alone) or timer.summary()) if run_timer else None
         if best is not None:
             roof = roofline(best, img_flops, args.batch, ms, args.precision)
             best2 = timer.summary(is_fwd_dgrad)
@@ -669,7 +741,7 @@ def main():
                            "as main.py:64's loss.item() does"},
                "step_mode": "hip-graph" if use_graph else "eager",
                "rccl": {"backend": dist.get_backend(), "world_size": dist.get_world_size()} if use_dp else None}
-        if world == 1 and not args.no_parity:
+        if world == 1 and run_parity:
             try:
                 dl, lp, lr = parity_c0(device)
                 out["loss_delta_vs_ref"] = {"abs": dl, "product": lp, "oracle": lr,
@@ -692,7 +764,7 @@ def main():
                                                               seconds=round(time.time() - t0, 1))
                 except Exception as e:
                     out["train_curve_vs_ref_headline"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and run_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())

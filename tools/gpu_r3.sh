@@ -6,6 +6,7 @@ set -o pipefail
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 TAG="${TAG:-r3}"
+OUT="${OUT:-results}"
 STEPS="${STEPS:-tests bench}"
 for s in $STEPS; do
   case $s in
@@ -18,8 +19,9 @@ for s in $STEPS; do
       timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke_${TAG}.log 2>&1 || { tail -30 gpurun_out/smoke_${TAG}.log; exit 1; }
       tail -1 gpurun_out/smoke_${TAG}.log ;;
     bench)
-      timeout -k 10 400 python -u bench.py > gpurun_out/bench_${TAG}.json 2> gpurun_out/bench_${TAG}.err || { tail -30 gpurun_out/bench_${TAG}.err; exit 1; }
-      cat gpurun_out/bench_${TAG}.json ;;
+      mkdir -p "$OUT"
+      timeout -k 10 400 python -u bench.py --full > "$OUT/bench_${TAG}.json" 2> "$OUT/bench_${TAG}.err" || { tail -30 "$OUT/bench_${TAG}.err"; exit 1; }
+      cat "$OUT/bench_${TAG}.json" ;;
     benchq)
       timeout -k 10 300 python -u bench.py --no-cpu-baseline --no-parity --steps 20 > gpurun_out/benchq_${TAG}.json 2> gpurun_out/benchq_${TAG}.err || { tail -30 gpurun_out/benchq_${TAG}.err; exit 1; }
       cat gpurun_out/benchq_${TAG}.json ;;

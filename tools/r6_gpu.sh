@@ -2,13 +2,14 @@
 # Round-6 GPU pass: the GPU test suite (parity records to gpurun_out/), then
 # optional extra steps named on the command line:
 #   curve   tools/curve_diag.py (C0 fp32 curve: which step / op leaves fp64)
-#   bench   default bench.py line (C2) into gpurun_out/bench_${TAG}.json
+#   bench   full bench.py line (C2, --full) into $OUT/bench_${TAG}.json (OUT defaults to results)
 #   prof    rocprofv3 kernel-trace summary of the C2 step
 #   c4      C4 bf16 / fp8 bench lines (tools/cfg_runs.sh)
 #   notests skip the test suite
 set -o pipefail
 mkdir -p gpurun_out
 TAG=${TAG:-r6}
+OUT=${OUT:-results}
 export TMPDIR=/tmp
 export MAECLIP_PARITY_OUT=$PWD/gpurun_out/parity_${TAG}.jsonl
 want() { for a in "${@:2}"; do [ "$a" = "$1" ] && return 0; done; return 1; }
@@ -23,9 +24,10 @@ if want curve "$@"; then
   cat gpurun_out/curve_diag_${TAG}.txt
 fi
 if want bench "$@"; then
-  timeout -k 10 600 python -u bench.py > gpurun_out/bench_${TAG}.json 2> gpurun_out/bench_${TAG}.err \
-    || { tail -30 gpurun_out/bench_${TAG}.err; exit 1; }
-  cat gpurun_out/bench_${TAG}.json
+  mkdir -p "$OUT"
+  timeout -k 10 600 python -u bench.py --full > "$OUT/bench_${TAG}.json" 2> "$OUT/bench_${TAG}.err" \
+    || { tail -30 "$OUT/bench_${TAG}.err"; exit 1; }
+  cat "$OUT/bench_${TAG}.json"
 fi
 if want prof "$@"; then
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_${TAG} -o run --output-format csv -- \
