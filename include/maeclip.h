@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MAECLIP_ABI_VERSION 11
+#define MAECLIP_ABI_VERSION 12
 #ifndef MAECLIP_F32
 #define MAECLIP_F32 0
 #define MAECLIP_BF16 1
@@ -230,12 +230,19 @@ int32_t maeclip_wgrad_grouped(const maeclip_wgrad_problem* probs, int32_t nprob,
  * (modeling_distilbert.py:125-145). qkv: [B*n, ld_qkv] token rows with q at
  * column h*hd, k at H*hd + h*hd, v at 2*H*hd + h*hd. o: [B*n, ld_o].
  * lse: [B, H, n] f32, log2-domain row log-sum-exp of scale*q.k (bwd input).
- * key_mask (optional, f32 [B, n]): 0 = padding key (forward; the backward
- * takes it only in fp32 at n beyond the LDS images -- the streamed "rows"
- * path -- and rejects it otherwise: the frozen text tower has no backward).
- * dropout_p applies to the probabilities in the forward only (DistilBERT
- * attention dropout; no bwd). fp32 forward / backward at any n: past the LDS
- * images (n ~ 540 at hd 32) 64-row blocks are streamed (no dropout there).
+ * key_mask (optional, f32 [B, n]): 0 = padding key, in the forward and in the
+ * backward (masked keys take P = 0: their dK / dV rows are zero). A sample
+ * whose mask has no valid key is out of scope (DistilBERT's CLS is always
+ * valid). dropout_p > 0 drops probabilities with the counter-based keep mask
+ * of (seed, *step_ptr, b*H + h, q, k), scaled by 1/(1-p); the backward redraws
+ * the same mask from the same seed / step value (ABI 12), so pass the
+ * forward's: dV = (M.P/(1-p))^T dO, dS = P.(M/(1-p).(dO V^T) - rowsum(dO.O)).
+ * The backward takes key_mask and dropout in bf16 and fp32 at head_dim 64 and
+ * n <= 256 (the two-phase MFMA kernel's own instantiations; deterministic, no
+ * atomics; the v-bias partial then comes from the dV it computes). Past that
+ * the fp32 streamed "rows" path takes the mask (no dropout) and everything
+ * else is rejected. fp32 forward / backward at any n: past the LDS images
+ * (n ~ 540 at hd 32) 64-row blocks are streamed (no dropout there).
  * bwd: dout [B*n, ld_o], dqkv [B*n, ld_dqkv]; colsum_partial optional
  * [B, 3*H*hd] per-sample column sums of dqkv (qkv bias gradient). */
 typedef struct {
@@ -380,6 +387,15 @@ int32_t maeclip_dropout(const float* x, float* y, int64_t M, int32_t D, int64_t 
  * (f32 [B*T], the attention kernels' key mask) in the same launch */
 int32_t maeclip_embed_fwd(const int64_t* ids, const float* word, const float* pos, int32_t B, int32_t T, int32_t D,
                           int64_t V, float* out, const int64_t* mask_in, float* mask_out, void* stream);
+/* its backward (ABI 12): dx f32 [B*T, D] -> dense dword [V, D] and dpos [P, D]
+ * (P >= T). Rows no token maps to are zero, position rows >= T are zero, and
+ * row padding_idx (-1: none; HF builds nn.Embedding(vocab, dim, padding_idx =
+ * pad_token_id = 0)) stays zero. Tokens of one id are added in ascending
+ * token order in fp32 by one workgroup and the row is written once: no
+ * atomics, bitwise reproducible. No workspace, allocation or synchronisation
+ * (capture-safe). ids are clamped to [0, V) as in the forward. */
+int32_t maeclip_embed_bwd(const float* dx, const int64_t* ids, int32_t B, int32_t T, int32_t D, int64_t V, int64_t P,
+                          int64_t padding_idx, float* dword, float* dpos, void* stream);
 
 /* ---------------------------------------------------------- multi-tensor */
 typedef struct {

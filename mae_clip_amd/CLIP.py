@@ -35,7 +35,7 @@ class CLIPModel(nn.Module):
         image_embedding = image_embedding or CFG.image_embedding
         text_embedding = text_embedding or CFG.text_embedding
         self.image_encoder = ImageEncoder()
-        self.text_encoder = TextEncoder()
+        self.text_encoder = TextEncoder(trainable=bool(CFG.text_trainable))
         if self.image_encoder.model.embed_dim != image_embedding:
             raise ValueError(f"image_embedding={image_embedding} but {CFG.model_name} has "
                              f"{self.image_encoder.model.embed_dim} features")
@@ -75,6 +75,8 @@ class CLIPModel(nn.Module):
             self.image_encoder.model.register_weights(c)
             if self.mae_decoder is not None:
                 self.mae_decoder.register_weights(c)
+            if self.text_encoder.model.trainable:
+                self.text_encoder.model.register_weights(c)
             self._cache = c
         return self._cache
 
@@ -112,7 +114,11 @@ class CLIPModel(nn.Module):
         # the frozen text tower (no autograd, own bf16 weights) is independent of
         # the image path: it runs on the side stream, overlapped with the image
         # encoder, and is issued first so it also overlaps the weight-shadow cast
-        use_side = bool(CFG.side_stream)
+        # A trainable text tower reads the weight shadows this forward refreshes
+        # and its backward is part of the autograd chain: it runs on the main
+        # stream, after the refresh.
+        text_train = self.text_encoder.model.trainable
+        use_side = bool(CFG.side_stream) and not text_train
         main = torch.cuda.current_stream(img.device)
         if use_side:
             side = Fn.side_stream(img.device)
@@ -132,13 +138,16 @@ class CLIPModel(nn.Module):
         else:
             tokens = vit.forward_tokens(img, dtype, cache, world=world)
             feat = Fn.EncoderHeadFn.apply(tokens, dtype, vit.fc_norm.weight, vit.fc_norm.bias, None, None)
+        snap = self.step_snaps[self.step % 8:self.step % 8 + 1] if self.training else None
         if use_side:
             main.wait_stream(side)
             text_features.record_stream(main)
+        elif text_train:
+            text_features = self.text_encoder(batch["input_ids"], batch["attention_mask"], seed=seed + 17,
+                                              dtype=dtype, step_ptr=sc, cache=cache, bwd_step_ptr=snap)
         else:
             text_features = self.text_encoder(batch["input_ids"], batch["attention_mask"], seed=seed + 17,
                                               dtype=dtype, step_ptr=sc)
-        snap = self.step_snaps[self.step % 8:self.step % 8 + 1] if self.training else None
         image_embeddings = self.image_projection(feat, seed=seed + 29, step_ptr=sc, bwd_step_ptr=snap)
         text_embeddings = self.text_projection(text_features, seed=seed + 31, step_ptr=sc, bwd_step_ptr=snap)
         clip = clip_loss(image_embeddings, text_embeddings, self.temperature,

@@ -61,6 +61,8 @@ text_vocab_size = 30522
 text_max_position = 512
 text_dropout = 0.1
 text_attention_dropout = 0.1
+text_trainable = False     # True: CLIPModel trains the text tower too (TextEncoder(trainable=True)); the
+                           # reference's CLIPModel leaves it frozen (modules.py:35), which stays the default
 
 # ---- numerics / determinism
 precision = "bf16"         # "bf16" (perf), "fp8" (C4: e4m3/e5m2 stack GEMMs, bf16 elsewhere) or "fp32" (parity mode)

@@ -663,7 +663,15 @@ attn_fwd_kernel(const maeclip_attn_args a) {
 // two-image LDS footprint would allow three.
 // WG = 16: up to 16 waves in the one workgroup a CU holds (the C4 decoder,
 // n = 577: 37 tiles, at most 3 per wave instead of 5; register budget 128).
-template <typename T, int HD, bool TWO_ = false, int OCC = 1, int WG = MAXW, bool Q8 = false>
+// MASKED / DROP (the trainable DistilBERT tower; instantiations of their own,
+// so the plain kernels keep their code and registers): key_mask zeroes P of
+// masked and padding keys in both phases (kvm[] in LDS: 1 = valid key); DROP
+// redraws the forward's keep mask M(q, k): dV = (M P sc)^T dO and
+// dS = P (M sc dP - rowsum(dO O)), so the dP accumulator starts at 0 instead
+// of -rowsum and the v-bias partial is the column sum of the dV tiles (rows
+// of M P sc do not sum to 1); the k-bias partial stays identically zero.
+template <typename T, int HD, bool TWO_ = false, int OCC = 1, int WG = MAXW, bool Q8 = false, bool MASKED = false,
+          bool DROP = false>
 __global__ void __launch_bounds__(WG * 64) __attribute__((amdgpu_waves_per_eu(WG > MAXW ? 4 : 2 * OCC)))
 attn_bwd_kernel(const maeclip_attn_args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -687,6 +695,20 @@ attn_bwd_kernel(const maeclip_attn_args a) {
   float* L2 = (float*)(smem + (TWO ? 2 : 4) * img);
   float* Dv = L2 + npad;
   float* cs = Dv + npad;  // [NW][3*HD] bias-grad partials
+  float* kvm = cs + NW * 3 * HD;  // MASKED: [npad] 1 = valid key, 0 = masked / padding
+  if constexpr (MASKED) {
+    for (int k = threadIdx.x; k < npad; k += NTH)
+      kvm[k] = (k < n && a.key_mask[(int64_t)b * n + k] != 0.f) ? 1.f : 0.f;
+  }
+  uint64_t dseed = 0, dbh = 0;
+  uint32_t dthr = 0;
+  float dsc = 1.f;
+  if constexpr (DROP) {
+    dseed = mc_step_seed(a.seed, a.step_ptr);
+    dbh = (uint64_t)b * H + h;
+    dthr = (uint32_t)((double)a.dropout_p * 4294967296.0);
+    dsc = 1.f / (1.f - a.dropout_p);
+  }
 
   const int HH = H * HD;
   const T* qkv = (const T*)a.qkv + (int64_t)b * n * a.ld_qkv;
@@ -698,9 +720,10 @@ attn_bwd_kernel(const maeclip_attn_args a) {
   const int nkt = (n + 15) >> 4;
   __syncthreads();
   ASTAMP(1);
-  if (a.colsum_partial && threadIdx.x < NW * HD) {
+  if (!DROP && a.colsum_partial && threadIdx.x < NW * HD) {
     // v-bias gradient: sum over keys of dV = sum over queries of dO (softmax
-    // rows sum to 1; the backward runs without attention dropout). Row group
+    // rows sum to 1, over the valid keys under a key mask; with dropout the
+    // partial comes from the dV tiles of phase 1 instead). Row group
     // r0 of column d -> cs[r0][2 HD + d]; the k-bias gradient is identically
     // zero (softmax is invariant to a per-query constant) and stays 0.
     constexpr int EPC = 16 / (int)sizeof(T);
@@ -715,10 +738,17 @@ attn_bwd_kernel(const maeclip_attn_args a) {
   T* dqkv = (T*)a.dqkv + (int64_t)b * n * a.ld_dqkv;
 
   // ---------------- phase 1: dK, dV (wave owns 16-key tiles)
+  float cv[HD / 16][4];  // DROP: per-lane running sum of this wave's dV rows (v-bias gradient)
+#pragma unroll
+  for (int dt = 0; dt < HD / 16; ++dt)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) cv[dt][i] = 0.f;
   for (int kt = wave; kt < nkt; kt += NW) {
     const int k0 = kt * 16;
     const int key = k0 + (lane & 15);
     const bool kok = key < n;
+    bool kvalid = true;
+    if constexpr (MASKED) kvalid = kvm[key] != 0.f;
     RowFrag<T, HD> kf[HD / 32], vf[HD / 32];
 #pragma unroll
     for (int ks = 0; ks < HD / 32; ++ks) {
@@ -741,7 +771,8 @@ attn_bwd_kernel(const maeclip_attn_args a) {
       for (int u = 0; u < 2; ++u) {
         const int q0 = qc + 16 * u;
         // row constants as the initial accumulators: s' = S - lse/c, dp' = dP - Dv
-        v4f s = *(const v4f*)(L2 + q0 + 4 * g), dp = *(const v4f*)(Dv + q0 + 4 * g);
+        const v4f dvq = *(const v4f*)(Dv + q0 + 4 * g);
+        v4f s = *(const v4f*)(L2 + q0 + 4 * g), dp = DROP ? v4f{0.f, 0.f, 0.f, 0.f} : dvq;
 #pragma unroll
         for (int ks = 0; ks < HD / 32; ++ks) {
           RowFrag<T, HD> qf, df;
@@ -754,9 +785,16 @@ attn_bwd_kernel(const maeclip_attn_args a) {
         // are never stored; padding queries have p = 0 (L2 = -1e30)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const float p = __builtin_amdgcn_exp2f(s[i] * c);
-          P[u][i] = p;
-          dS[u][i] = p * dp[i];
+          float p = __builtin_amdgcn_exp2f(s[i] * c);
+          if constexpr (MASKED) p = kvalid ? p : 0.f;   // a select: exp2 of a masked key's score may overflow
+          if constexpr (DROP) {
+            const bool keep = dropout_keep(dseed, dbh, q0 + 4 * g + i, key, dthr);
+            P[u][i] = keep ? p * dsc : 0.f;
+            dS[u][i] = p * ((keep ? dp[i] * dsc : 0.f) + dvq[i]);
+          } else {
+            P[u][i] = p;
+            dS[u][i] = p * dp[i];
+          }
         }
       }
 #pragma unroll
@@ -782,6 +820,27 @@ attn_bwd_kernel(const maeclip_attn_args a) {
         st4<T>(rowp + HH + 16 * dt + 4 * g, dk[dt] * a.scale);
         st4<T>(rowp + 2 * HH + 16 * dt + 4 * g, dv[dt]);
       }
+      if constexpr (DROP) {
+#pragma unroll
+        for (int dt = 0; dt < HD / 16; ++dt)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) cv[dt][i] += dv[dt][i];
+      }
+    }
+  }
+  if constexpr (DROP) {
+    if (a.colsum_partial) {
+      // v-bias gradient from the dV rows this wave computed (fixed order: the
+      // wave's tiles, then the 16 key lanes, then the waves below)
+#pragma unroll
+      for (int dt = 0; dt < HD / 16; ++dt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          float sv = cv[dt][i];
+#pragma unroll
+          for (int o = 1; o < 16; o <<= 1) sv += __shfl_xor(sv, o, 64);
+          if ((lane & 15) == 0) cs[wave * 3 * HD + 2 * HD + 16 * dt + 4 * g + i] = sv;
+        }
     }
   }
 
@@ -826,6 +885,7 @@ attn_bwd_kernel(const maeclip_attn_args a) {
       for (int u = 0; u < 2; ++u) {
         const int kb = kc + 16 * u;
         v4f s = {lq, lq, lq, lq}, dp = {dq_, dq_, dq_, dq_};
+        if constexpr (DROP) dp = v4f{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < HD / 32; ++ks) {
           RowFrag<T, HD> kf, vf;
@@ -834,8 +894,21 @@ attn_bwd_kernel(const maeclip_attn_args a) {
           s = mma32(kf, qf[ks], s);    // S^T[key=4g+i][q=lane&15]
           dp = mma32(vf, df[ks], dp);  // dP^T
         }
+        if constexpr (DROP) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const bool keep = dropout_keep(dseed, dbh, q, kb + 4 * g + i, dthr);
+            dp[i] = (keep ? dp[i] * dsc : 0.f) + dq_;
+          }
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) dST[u][i] = __builtin_amdgcn_exp2f(s[i] * c) * dp[i];
+        if constexpr (MASKED) {
+          // masked and padding keys: P = 0 (a select, as below)
+          const v4f kq = *(const v4f*)(kvm + kb + 4 * g);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) dST[u][i] = kq[i] != 0.f ? dST[u][i] : 0.f;
+        }
         // padding keys (last chunk only): K rows are zero, but an overflowing
         // exp2(-lse) would turn 0 * inf into NaN in dQ, so zero them explicitly
         if (kb + 16 > n) {
@@ -1456,7 +1529,7 @@ __global__ void __launch_bounds__(256) attn_rows_colsum_kernel(const maeclip_att
 
 template <int HD>
 int run_rows(const maeclip_attn_args& a, bool bwd, hipStream_t s) {
-  MC_CHECK_ARG(bwd || a.dropout_p == 0.f, "maeclip_attn_fwd: the fp32 long-sequence path has no attention dropout");
+  MC_CHECK_ARG(a.dropout_p == 0.f, "maeclip_attn: the fp32 long-sequence path has no attention dropout");
   const dim3 grid((unsigned)((a.n + RB - 1) / RB), (unsigned)(a.B * a.H));
   if (!bwd) {
     hipLaunchKernelGGL(attn_fwd_rows_kernel<HD>, grid, dim3(RB), 0, s, a);
@@ -1485,10 +1558,10 @@ template <typename T, int HD> size_t fwd_lds(int n) {
   const int nimg = fwd_qimg<T, HD>(npad) ? 3 : 2;   // K, V (+ Q; the 16-wave launches ignore the third)
   return (size_t)nimg * npad * Img<T, HD>::ROWB + (size_t)npad * 4;
 }
-template <typename T, int HD> size_t bwd_lds(int n, int nw, bool two = false) {
+template <typename T, int HD> size_t bwd_lds(int n, int nw, bool two = false, bool masked = false) {
   const int npad = (n + 31) & ~31;
   const int nimg = (std::is_same<T, bf16_t>::value && !two) ? 4 : 2;
-  return (size_t)nimg * npad * Img<T, HD>::ROWB + (size_t)2 * npad * 4 + (size_t)nw * 3 * HD * 4;
+  return (size_t)nimg * npad * Img<T, HD>::ROWB + (size_t)(masked ? 3 : 2) * npad * 4 + (size_t)nw * 3 * HD * 4;
 }
 
 template <typename T, int HD, bool TWO = false, int OCC = 1, int WG = MAXW, bool Q8 = false>
@@ -1496,6 +1569,14 @@ void launch_bwd(const maeclip_attn_args& a, dim3 grid, int nthreads, size_t lds,
   if (lds > 65536)
     maeclip::allow_lds((const void*)attn_bwd_kernel<T, HD, TWO, OCC, WG, Q8>, (int)lds);
   hipLaunchKernelGGL((attn_bwd_kernel<T, HD, TWO, OCC, WG, Q8>), grid, dim3(nthreads), lds, s, a);
+}
+
+// masked / dropout backward (four images in bf16, two in fp32; 8 waves)
+template <typename T, int HD, bool MASKED, bool DROP>
+void launch_bwd_md(const maeclip_attn_args& a, dim3 grid, int nthreads, size_t lds, hipStream_t s) {
+  if (lds > 65536)
+    maeclip::allow_lds((const void*)attn_bwd_kernel<T, HD, false, 1, MAXW, false, MASKED, DROP>, (int)lds);
+  hipLaunchKernelGGL((attn_bwd_kernel<T, HD, false, 1, MAXW, false, MASKED, DROP>), grid, dim3(nthreads), lds, s, a);
 }
 
 // resident workgroups per CU of a bwd variant (registers, waves and LDS)
@@ -1555,9 +1636,27 @@ int run(const maeclip_attn_args& a, bool bwd, hipStream_t s, bool& q8_done) {
     // fp32 beyond the LDS images (option ATTN_ROWS = 1 forces it: tests)
     if (lds > 163840 || maeclip::option(MAECLIP_OPT_ATTN_ROWS, 0) != 0) return run_rows<HD>(a, bwd, s);
   }
-  MC_CHECK_ARG(lds <= 163840, "maeclip_attn: n=%d needs %zu B of LDS (> 160 KiB)", a.n, lds);
-  MC_CHECK_ARG(!bwd || !a.key_mask, "maeclip_attn_bwd: key_mask is supported by the fp32 rows path only");
   dim3 grid((unsigned)(a.B * a.H));
+  if (bwd && (a.key_mask || a.dropout_p > 0.f)) {
+    // the trainable text tower's backward: its own instantiations of the
+    // two-phase kernel (npad <= 256 at head_dim 64: 137 KiB of LDS in bf16,
+    // 145 KiB in fp32)
+    MC_CHECK_ARG(HD == 64 && a.n <= 256,
+                 "maeclip_attn_bwd: key_mask / dropout need head_dim 64 and n <= 256 (got head_dim %d, n %d); "
+                 "past that only the fp32 rows path takes a key_mask", HD, a.n);
+    MC_CHECK_ARG(a.dropout_p < 1.f, "maeclip_attn_bwd: dropout_p must be < 1");
+    if constexpr (HD == 64) {
+      const size_t lm = bwd_lds<T, HD>(a.n, nw, !std::is_same<T, bf16_t>::value, true);
+      MC_CHECK_ARG(lm <= 163840, "maeclip_attn_bwd: n=%d needs %zu B of LDS (> 160 KiB)", a.n, lm);
+      const bool drop = a.dropout_p > 0.f;
+      if (a.key_mask && drop) launch_bwd_md<T, HD, true, true>(a, grid, nthreads, lm, s);
+      else if (a.key_mask) launch_bwd_md<T, HD, true, false>(a, grid, nthreads, lm, s);
+      else launch_bwd_md<T, HD, false, true>(a, grid, nthreads, lm, s);
+      MC_CHECK_LAUNCH("maeclip_attn_bwd(mask / dropout)");
+    }
+    return 0;
+  }
+  MC_CHECK_ARG(lds <= 163840, "maeclip_attn: n=%d needs %zu B of LDS (> 160 KiB)", a.n, lds);
   if constexpr (std::is_same<T, bf16_t>::value) {
     // one-pass diagonal backward: the default at HD 32 up to npad 256
     // (MAECLIP_ATTN_DIAG=0 turns it off). HD 64 (LDS fits up to npad 224): the

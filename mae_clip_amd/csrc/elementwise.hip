@@ -142,6 +142,70 @@ __global__ void __launch_bounds__(NTH) embed_kernel(const int64_t* __restrict__ 
   *(v4f*)(out + row * D + d) = w + pp;
 }
 
+// Backward of embed_kernel: dense word / position gradients without atomics.
+// zero_rows_kernel clears the word table's gradient; embed_bwd_word_kernel
+// then writes every row some token maps to exactly once. Block (i, column
+// tile): token i owns the row of its id iff no earlier token has that id (a
+// scan of ids[0..i)); the owner walks ids[i..M) in 256-token chunks, every
+// wave ballots its 64 matches, and each thread adds its column of the matching
+// dx rows in ascending token order (fp32) -- the order is a function of ids
+// alone, so the result is bitwise reproducible. No sort and no workspace:
+// nothing to allocate under graph capture; M blocks x M / 256 chunk steps
+// (M = 6400 at B 256, T 25). The id is clamped as in the forward.
+__global__ void __launch_bounds__(NTH) zero_rows_kernel(float* __restrict__ p, int64_t n4) {
+  for (int64_t i = (int64_t)blockIdx.x * NTH + threadIdx.x; i < n4; i += (int64_t)gridDim.x * NTH)
+    ((v4f*)p)[i] = v4f{0.f, 0.f, 0.f, 0.f};
+}
+
+__device__ __forceinline__ int64_t embed_clamp(int64_t id, int64_t V) { return id < 0 ? 0 : (id >= V ? V - 1 : id); }
+
+__global__ void __launch_bounds__(256) embed_bwd_word_kernel(const float* __restrict__ dx,
+                                                             const int64_t* __restrict__ ids, int64_t M, int D,
+                                                             int64_t V, int64_t padding_idx,
+                                                             float* __restrict__ dword) {
+  __shared__ unsigned long long masks[4];
+  const int64_t i = blockIdx.x;
+  const int col = blockIdx.y * 256 + threadIdx.x;
+  const int64_t id = embed_clamp(ids[i], V);
+  if (id == padding_idx) return;   // block-uniform
+  int earlier = 0;
+  for (int64_t j = threadIdx.x; j < i; j += 256) earlier |= embed_clamp(ids[j], V) == id;
+  if (__syncthreads_or(earlier)) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float acc = 0.f;
+  for (int64_t j0 = i & ~(int64_t)255; j0 < M; j0 += 256) {
+    const int64_t j = j0 + threadIdx.x;
+    const bool hit = j >= i && j < M && embed_clamp(ids[j], V) == id;
+    const unsigned long long m = __ballot(hit);
+    __syncthreads();   // the previous chunk's masks are read
+    if (lane == 0) masks[wave] = m;
+    __syncthreads();
+    if (col < D) {
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        unsigned long long mm = masks[w];
+        while (mm) {
+          const int k = __ffsll((long long)mm) - 1;
+          mm &= mm - 1;
+          acc += dx[(j0 + 64 * w + k) * D + col];
+        }
+      }
+    }
+  }
+  if (col < D) dword[id * D + col] = acc;
+}
+
+// dpos[t] = sum over b (ascending) of dx[b*T + t] for t < T, zero rows past T
+__global__ void __launch_bounds__(256) embed_bwd_pos_kernel(const float* __restrict__ dx, int B, int T, int D,
+                                                            float* __restrict__ dpos) {
+  const int t = blockIdx.x, col = blockIdx.y * 256 + threadIdx.x;
+  if (col >= D) return;
+  float acc = 0.f;
+  if (t < T)
+    for (int b = 0; b < B; ++b) acc += dx[((int64_t)b * T + t) * D + col];
+  dpos[(int64_t)t * D + col] = acc;
+}
+
 
 // colsum partials of a row matrix (bias gradient of a Linear whose output
 // gradient arrives un-reduced), optionally emitting a bf16 copy of the rows.
@@ -467,6 +531,23 @@ extern "C" int32_t maeclip_embed_fwd(const int64_t* ids, const float* word, cons
   hipLaunchKernelGGL(embed_kernel, dim3((D / 4 + NTH - 1) / NTH, (unsigned)(B * T)), dim3(NTH), 0, (hipStream_t)stream, ids,
                      word, pos, T, D, V, out, mask_in, mask_out);
   MC_CHECK_LAUNCH("maeclip_embed_fwd");
+  return 0;
+}
+
+extern "C" int32_t maeclip_embed_bwd(const float* dx, const int64_t* ids, int32_t B, int32_t T, int32_t D, int64_t V,
+                                     int64_t P, int64_t padding_idx, float* dword, float* dpos, void* stream) {
+  MC_CHECK_ARG(dx && ids && dword && dpos && B > 0 && T > 0 && D > 0 && D % 4 == 0 && V > 0 && P >= T,
+               "maeclip_embed_bwd: bad args (D %% 4 == 0, T <= P)");
+  MC_CHECK_ARG(padding_idx >= -1 && padding_idx < V, "maeclip_embed_bwd: padding_idx must be -1 (none) or a row of the table");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t n4 = V * D / 4, M = (int64_t)B * T;
+  const unsigned ct = (unsigned)((D + 255) / 256);
+  const int64_t zb = (n4 + NTH - 1) / NTH;
+  hipLaunchKernelGGL(zero_rows_kernel, dim3((unsigned)(zb < 4096 ? zb : 4096)), dim3(NTH), 0, s, dword, n4);
+  hipLaunchKernelGGL(embed_bwd_word_kernel, dim3((unsigned)M, ct), dim3(256), 0, s, dx, ids, M, (int)D, V, padding_idx,
+                     dword);
+  hipLaunchKernelGGL(embed_bwd_pos_kernel, dim3((unsigned)P, ct), dim3(256), 0, s, dx, (int)B, (int)T, (int)D, dpos);
+  MC_CHECK_LAUNCH("maeclip_embed_bwd");
   return 0;
 }
 

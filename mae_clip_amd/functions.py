@@ -13,6 +13,7 @@ Reference ops replaced (file:line):
   EncoderHeadFn       timm global_pool="avg" + fc_norm; MAE mae_norm
   DecoderEmbedFn      HF decoder_embed + mask-token unshuffle + pos (:536-566)
   MaeHeadLossFn       HF decoder_norm + decoder_pred + loss (:568-578, :852-859)
+  TextStackFn         HF DistilBertModel, trainable (modules.py:34-51 with trainable=True)
   ProjectionHeadFn    modules.py:69-76 (always fp32)
   ClipLossFn          CLIP.py:34-43
 """
@@ -585,6 +586,179 @@ class TransformerStackFn(torch.autograd.Function):
         g = bufs[0]["dx"]
         ctx.saved = None
         return (g.view(B, n, D), None, *grads)
+
+
+# ------------------------------------------------------------ text tower
+@dataclass
+class TextSpec:
+    B: int
+    T: int
+    D: int
+    H: int
+    dtype: torch.dtype              # compute dtype of GEMM operands / activations
+    wT: list                        # per layer: (q|k|v [3D, D], out_lin, lin1, lin2) weights in `dtype`
+    p_drop: float = 0.0             # embeddings / FFN dropout (0 in eval mode)
+    p_attn: float = 0.0             # attention-probability dropout
+    seed: int = 0
+    step_ptr: torch.Tensor = None   # device step counter keying the dropout masks
+    bwd_step_ptr: torch.Tensor = None   # the same step's value as the backward will find it (snapshot slot)
+    padding_idx: int = 0            # HF: nn.Embedding(vocab, dim, padding_idx=pad_token_id)
+    eps: float = 1e-12
+    grouped_wgrad: bool = True
+    side: bool = True
+
+
+TEXT_EMB = 4        # word_embeddings, position_embeddings, LayerNorm.weight, LayerNorm.bias
+TEXT_PER_LAYER = 16  # (q, k, v, out)_lin.(weight, bias), sa_layer_norm.(w, b), lin1.(w, b), lin2.(w, b), output_layer_norm.(w, b)
+
+
+class TextStackFn(torch.autograd.Function):
+    """HF DistilBertModel (modeling_distilbert.py: Embeddings + n post-LN
+    TransformerBlocks, LN(x + sublayer(x)), eps 1e-12) as one Function:
+    last_hidden_state [B, T, D] (f32). The seeds are the frozen forward's
+    (modules.DistilBertModel); the backward redraws the three kinds of dropout
+    mask (embedding LN output, attention probabilities, FFN output) from them
+    and from the forward's step value (bwd_step_ptr, else a copy kept here)."""
+
+    @staticmethod
+    def forward(ctx, ids, am, spec: TextSpec, *params):
+        B, T, D, H = spec.B, spec.T, spec.D, spec.H
+        hd = D // H
+        dt = spec.dtype
+        bf = dt == torch.bfloat16
+        M = B * T
+        dev = ids.device
+        word, pos, eg, eb = params[:TEXT_EMB]
+        s0 = spec.seed * 131
+        x = K.embed_fwd(ids, word, pos)
+        h, m0, r0, hT, _ = K.ln_fwd(x, eg, eb, spec.eps, out_dtype=torch.float32, out_dropout=spec.p_drop,
+                                    seed_out=s0 + 1, y2=bf, step_ptr=spec.step_ptr)
+        hT = hT if bf else h
+        saved = []
+        for li, (wqkv, wout, w1, w2) in enumerate(spec.wT):
+            p = params[TEXT_EMB + li * TEXT_PER_LAYER:TEXT_EMB + (li + 1) * TEXT_PER_LAYER]
+            bqkv = torch.cat([p[1], p[3], p[5]])
+            qkv = K.linear_fwd(hT, wqkv, bqkv)
+            o, lse = K.attn_fwd(qkv, B, T, H, hd, hd ** -0.5, key_mask=am, dropout_p=spec.p_attn,
+                                seed=s0 + 7 * li + 2, step_ptr=spec.step_ptr)
+            sa = K.linear_fwd(o, wout, p[7], out_dtype=torch.float32)
+            a, m1, r1, aT, z1 = K.ln_fwd(sa, p[8], p[9], spec.eps, out_dtype=torch.float32, res=h, y2=bf, xsum=True)
+            del sa
+            aT = aT if bf else a
+            # lin1 epilogue: f1 = gelu(.), dgelu = gelu'(.) saved for the backward
+            dgelu = torch.empty((M, w1.shape[0]), device=dev, dtype=dt)
+            f1 = K.linear_fwd(aT, w1, p[11], epilogue=K.EPI_GELU_D, aux_out=dgelu)
+            f2 = K.linear_fwd(f1, w2, p[13], out_dtype=torch.float32)
+            hn, m2, r2, hnT, z2 = K.ln_fwd(f2, p[14], p[15], spec.eps, out_dtype=torch.float32, res=a,
+                                           in_dropout=spec.p_drop, seed_in=s0 + 7 * li + 3, y2=bf, xsum=True,
+                                           step_ptr=spec.step_ptr)
+            del f2, a
+            saved.append([hT, qkv, o, lse, z1, m1, r1, aT, dgelu, f1, z2, m2, r2])
+            h, hT = hn, (hnT if bf else hn)
+        ctx.emb = (ids, am, x, m0, r0)
+        ctx.saved = saved
+        ctx.spec = spec
+        ctx.params = params
+        ctx.arena = _arena()
+        # the step counter advances at the end of the model's forward: the
+        # backward redraws this forward's masks from a snapshot of the step
+        ctx.step_snap = None
+        if spec.step_ptr is not None and (spec.p_drop > 0 or spec.p_attn > 0):
+            ctx.step_snap = spec.bwd_step_ptr if spec.bwd_step_ptr is not None else spec.step_ptr.clone()
+        return h.view(B, T, D)
+
+    @staticmethod
+    def backward(ctx, gy):
+        spec = ctx.spec
+        B, T, D, H = spec.B, spec.T, spec.D, spec.H
+        hd = D // H
+        bf = spec.dtype == torch.bfloat16
+        M = B * T
+        params = ctx.params
+        ar = ctx.arena
+        snap = ctx.step_snap
+        s0 = spec.seed * 131
+        ids, am, x, m0, r0 = ctx.emb
+        dev = gy.device
+        grads = [None] * len(params)
+        rb = K.ReduceBatch()
+        wq = WgradQueue(dev, spec.side, spec.grouped_wgrad)
+        qkv_bias = []    # (fused q|k|v bias gradient [3D], its three parameters)
+        g = gy.reshape(M, D)
+        if not g.is_contiguous():
+            g = g.contiguous()
+        for li in reversed(range(len(spec.wT))):
+            wqkv, wout, w1, w2 = spec.wT[li]
+            base = TEXT_EMB + li * TEXT_PER_LAYER
+            p = params[base:base + TEXT_PER_LAYER]
+            hT, qkv, o, lse, z1, m1, r1, aT, dgelu, f1, z2, m2, r2 = ctx.saved[li]
+            gi = [None] * TEXT_PER_LAYER
+            # output_layer_norm: h' = LN(z2), z2 = dropout(f2) + a
+            if spec.p_drop > 0:
+                dz2, _, pg, pb, _ = K.ln_bwd(g, z2, m2, r2, p[14])
+                df2 = K.dropout(dz2, spec.p_drop, s0 + 7 * li + 3, step_ptr=snap)
+                df2T = torch.empty((M, D), device=dev, dtype=torch.bfloat16) if bf else None
+                cpart = K.rows_colsum(df2, out_bf16=df2T)
+                df2T = df2T if bf else df2
+                del df2
+            else:
+                dz2, df2T, pg, pb, cpart = K.ln_bwd(g, z2, m2, r2, p[14], want_bf16=bf, want_colsum=True)
+                df2T = df2T if bf else dz2
+            gi[14], gi[15] = rb.add(pg, out=gout(ar, p[14])), rb.add(pb, out=gout(ar, p[15]))
+            # ffn.lin2 (+ GELU backward fused into the dgrad epilogue)
+            gi[13] = rb.add(cpart, out=gout(ar, p[13]))
+            dA_part = torch.empty((K.gemm_colsum_rows(M), w1.shape[0]), device=dev, dtype=torch.float32)
+            dA = K.linear_dgrad(df2T, w2, epilogue=K.EPI_MUL_AUX, aux=dgelu, colsum=dA_part)
+            gi[12] = wq.wgrad(df2T, f1, out=gout(ar, p[12]))
+            del dgelu, f1
+            # ffn.lin1; the gradient of a is the FFN's plus the residual's (dz2)
+            gi[11] = rb.add(dA_part, out=gout(ar, p[11]))
+            da = K.linear_dgrad(dA, w1, out_dtype=torch.float32, epilogue=K.EPI_RESID, resid=dz2)
+            gi[10] = wq.wgrad(dA, aT, out=gout(ar, p[10]))
+            del dA, dz2
+            # sa_layer_norm: a = LN(z1), z1 = out_lin(attention) + h
+            dz1, dz1T, pg, pb, pc = K.ln_bwd(da, z1, m1, r1, p[8], want_bf16=bf, want_colsum=True)
+            dz1T = dz1T if bf else dz1
+            gi[8], gi[9] = rb.add(pg, out=gout(ar, p[8])), rb.add(pb, out=gout(ar, p[9]))
+            # attention.out_lin
+            gi[7] = rb.add(pc, out=gout(ar, p[7]))
+            dO = K.linear_dgrad(dz1T, wout)
+            gi[6] = wq.wgrad(dz1T, o, out=gout(ar, p[6]))
+            # attention (key mask + the forward's dropout mask redrawn)
+            dqkv, qpart = K.attn_bwd(qkv, o, dO, lse, B, T, H, hd, hd ** -0.5, key_mask=am, dropout_p=spec.p_attn,
+                                     seed=s0 + 7 * li + 2, step_ptr=snap)
+            del dO
+            qkv_bias.append((rb.add(qpart), (p[1], p[3], p[5])))
+            # q|k|v: one dgrad on the fused weight (+ the residual gradient dz1);
+            # the three weight gradients are column slices of dqkv times hT
+            g = K.linear_dgrad(dqkv, wqkv, out_dtype=torch.float32, epilogue=K.EPI_RESID, resid=dz1)
+            for j in range(3):
+                gi[2 * j] = wq.wgrad(dqkv[:, j * D:(j + 1) * D], hT, out=gout(ar, p[2 * j]))
+            del dqkv, dz1
+            ctx.saved[li] = None
+            for j in range(TEXT_PER_LAYER):
+                grads[base + j] = gi[j]
+        # embeddings: h0 = dropout(LN(word + pos))
+        word, pos, eg, eb = params[:TEXT_EMB]
+        if spec.p_drop > 0:
+            g = K.dropout(g, spec.p_drop, s0 + 1, step_ptr=snap)
+        dx, _, pg, pb, _ = K.ln_bwd(g, x, m0, r0, eg)
+        grads[2], grads[3] = rb.add(pg, out=gout(ar, eg)), rb.add(pb, out=gout(ar, eb))
+        grads[0], grads[1] = K.embed_bwd(dx, ids, word, pos, padding_idx=spec.padding_idx, dword=gout(ar, word),
+                                         dpos=gout(ar, pos))
+        rb.flush()
+        wq.join()
+        # the q / k / v bias gradients are the three thirds of the reduced partial
+        for li, (b3, ps) in zip(reversed(range(len(spec.wT))), qkv_bias):
+            base = TEXT_EMB + li * TEXT_PER_LAYER
+            for j, pj in enumerate(ps):
+                part = b3[j * D:(j + 1) * D]
+                grads[base + 2 * j + 1] = part if ar is None else K.copy_words(part, gout(ar, pj))
+        for i, (gr, pr) in enumerate(zip(grads, params)):
+            grads[i] = gr.view(pr.shape)
+        ctx.saved = None
+        ctx.emb = None
+        return (None, None, None, *grads)
 
 
 # ------------------------------------------------------------ patch embed

@@ -508,6 +508,27 @@ def embed_fwd(ids, word, pos, mask=None):
     return out if mask is None else (out, mo)
 
 
+def embed_bwd(dx, ids, word, pos, padding_idx=-1, dword=None, dpos=None):
+    """Dense gradients (dword [V, D], dpos [P, D], f32) of embed_fwd for dx
+    [B*T, D] f32: rows no token maps to, row `padding_idx` (-1: none) and
+    position rows >= T are zero; bitwise reproducible (no atomics)."""
+    _dev(dx, ids, dword, dpos)
+    B, T = ids.shape
+    V, D = word.shape
+    P = pos.shape[0]
+    if dx.dtype != torch.float32 or dx.shape != (B * T, D) or not dx.is_contiguous() or ids.dtype != torch.int64 \
+            or not ids.is_contiguous():
+        raise ValueError("embed_bwd: dx must be dense f32 [B*T, D] and ids dense int64 [B, T]")
+    dword = dword if dword is not None else torch.empty((V, D), device=dx.device, dtype=torch.float32)
+    dpos = dpos if dpos is not None else torch.empty((P, D), device=dx.device, dtype=torch.float32)
+    if dword.shape != (V, D) or dpos.shape != (P, D) or not (dword.is_contiguous() and dpos.is_contiguous()) \
+            or dword.dtype != torch.float32 or dpos.dtype != torch.float32:
+        raise ValueError("embed_bwd: dword [V, D] / dpos [P, D] must be dense f32")
+    _call("maeclip_embed_bwd", dx.data_ptr(), ids.data_ptr(), B, T, D, V, P, int(padding_idx), dword.data_ptr(),
+          dpos.data_ptr(), _stream())
+    return dword, dpos
+
+
 # -------------------------------------------------------------- LayerNorm
 def ln_fwd(x, gamma, beta, eps, out_dtype=None, res=None, in_dropout=0.0, out_dropout=0.0, seed_in=0, seed_out=0,
            want_stats=True, y2=False, xsum=False, step_ptr=None, q8=None, y_out=None, mean_out=None, rstd_out=None):
@@ -592,9 +613,11 @@ def attn_fwd(qkv, B, n, H, hd, scale, key_mask=None, dropout_p=0.0, seed=0, want
 
 
 def attn_bwd(qkv, o, dout, lse, B, n, H, hd, scale, want_colsum=True, key_mask=None, dqkv_out=None, part_out=None,
-             q8=None):
+             q8=None, dropout_p=0.0, seed=0, step_ptr=None):
     """(dqkv, bias-gradient partials); q8 (Fp8Blocks [B*n, 3*H*hd], optional):
-    the fp8 blocks of dqkv as stored (the qkv dgrad GEMM's operand)."""
+    the fp8 blocks of dqkv as stored (the qkv dgrad GEMM's operand).
+    key_mask / dropout_p, seed, step_ptr: the forward's (the keep mask is
+    redrawn; step_ptr must hold the value the forward ran with)."""
     _dev(qkv, o, dout, lse, key_mask)
     D = H * hd
     dqkv = dqkv_out if dqkv_out is not None else torch.empty((B * n, 3 * D), device=qkv.device, dtype=qkv.dtype)
@@ -604,7 +627,8 @@ def attn_bwd(qkv, o, dout, lse, B, n, H, hd, scale, want_colsum=True, key_mask=N
         if want_colsum else None
     a = L.AttnArgs(qkv=qkv.data_ptr(), o=o.data_ptr(), lse=lse.data_ptr(), dout=dout.data_ptr(), dqkv=dqkv.data_ptr(),
                    key_mask=_ptr(key_mask), colsum_partial=_ptr(part), ld_qkv=qkv.stride(0), ld_o=o.stride(0),
-                   ld_dqkv=3 * D, B=B, n=n, H=H, head_dim=hd, dtype=_dt(qkv), scale=scale, dropout_p=0.0, seed=0)
+                   ld_dqkv=3 * D, B=B, n=n, H=H, head_dim=hd, dtype=_dt(qkv), scale=scale, dropout_p=dropout_p,
+                   seed=int(seed), step_ptr=_ptr(step_ptr))
     _set_q8(a, q8)
     _call("maeclip_attn_bwd", C.byref(a), _stream())
     return dqkv, part

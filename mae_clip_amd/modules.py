@@ -153,6 +153,19 @@ class WeightCache:
             return p if shape2d is None else p.view(shape2d)
         return self.views[id(p)]
 
+    def fused_rows(self, ps, dtype):
+        """The weights ps (registered consecutively, equal row length) stacked
+        along the rows: one view of their adjacent bf16 shadows (kept current
+        by the fused AdamW like any shadow), or an fp32 concatenation made now."""
+        if dtype == torch.float32:
+            return torch.cat([p.detach() for p in ps], 0)
+        vs = [self.views[id(p)] for p in ps]
+        for a, b in zip(vs, vs[1:]):
+            if b.data_ptr() != a.data_ptr() + a.numel() * a.element_size():
+                raise RuntimeError("WeightCache.fused_rows: the weights were not registered consecutively")
+        off = (vs[0].data_ptr() - self.buf.data_ptr()) // self.buf.element_size()
+        return self.buf[off:off + sum(v.numel() for v in vs)].view(-1, vs[0].shape[1])
+
     def get_fp8(self, p: torch.Tensor):
         """(W, W^T) fp8 operands of GEMM weight p [N, K] for this step: the
         ones refresh() quantised (registered weights), else quantised now."""
@@ -360,6 +373,9 @@ class ImageEncoder(nn.Module):
 class DistilBertEmbeddings(nn.Module):
     def __init__(self, vocab, dim, max_pos):
         super().__init__()
+        # HF: nn.Embedding(vocab, dim, padding_idx=pad_token_id = 0); the trainable
+        # tower's backward leaves that row's gradient zero (TextSpec.padding_idx).
+        # The init below draws the row like every other, as the frozen tower did.
         self.word_embeddings = nn.Embedding(vocab, dim)
         self.position_embeddings = nn.Embedding(max_pos, dim)
         self.LayerNorm = nn.LayerNorm(dim, eps=1e-12)
@@ -399,13 +415,19 @@ class Transformer(nn.Module):
 
 
 class DistilBertModel(nn.Module):
-    """HF DistilBertModel parameter layout; forward-only (the reference freezes it,
-    modules.py:35,42-43). Dropout (p=0.1 embeddings/attention/FFN) follows
-    self.training like HF."""
+    """HF DistilBertModel parameter layout. trainable=False (the reference's
+    default, modules.py:35,42-43): forward-only launches under no_grad with
+    cached fused weights; trainable=True: functions.TextStackFn, under
+    autograd, with bf16 weight shadows from a WeightCache. Dropout (p=0.1
+    embeddings/attention/FFN) follows self.training like HF."""
+
+    pad_token_id = 0   # DistilBertConfig.pad_token_id: the word embedding's padding_idx
 
     def __init__(self, n_layers=None, dim=768, heads=None, hidden=None, vocab=None, max_pos=None, dropout=None,
-                 attention_dropout=None):
+                 attention_dropout=None, trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
+        self._cache = None
         self.n_layers = n_layers or CFG.text_layers
         self.dim = dim
         self.n_heads = heads or CFG.text_heads
@@ -439,8 +461,59 @@ class DistilBertModel(nn.Module):
             self._wc_key = key
         return self._wc
 
+    def register_weights(self, cache: WeightCache):
+        """GEMM weights of the trainable tower; q, k, v consecutively, so their
+        shadows are one [3D, D] operand (WeightCache.fused_rows)."""
+        for lyr in self.transformer.layer:
+            at = lyr.attention
+            for lin in (at.q_lin, at.k_lin, at.v_lin, at.out_lin, lyr.ffn.lin1, lyr.ffn.lin2):
+                cache.register(lin.weight, lin.weight.shape)
+
+    def stack_params(self):
+        emb = self.embeddings
+        ps = [emb.word_embeddings.weight, emb.position_embeddings.weight, emb.LayerNorm.weight, emb.LayerNorm.bias]
+        for lyr in self.transformer.layer:
+            at = lyr.attention
+            for m in (at.q_lin, at.k_lin, at.v_lin, at.out_lin, lyr.sa_layer_norm, lyr.ffn.lin1, lyr.ffn.lin2,
+                      lyr.output_layer_norm):
+                ps += [m.weight, m.bias]
+        return ps
+
+    def forward(self, input_ids, attention_mask, dtype=None, seed=0, step_ptr=None, cache=None, bwd_step_ptr=None):
+        """Returns last_hidden_state [B, T, dim] (f32). cache: the WeightCache
+        this tower's weights are registered in and that the caller refreshed
+        (CLIPModel's); None: the tower's own. bwd_step_ptr: as ProjectionHead."""
+        if not self.trainable:
+            return self._forward_frozen(input_ids, attention_mask, dtype=dtype, seed=seed, step_ptr=step_ptr)
+        _require_device(input_ids, "input_ids")
+        dtype = dtype or compute_dtype(self.precision)
+        if cache is None:
+            if self._cache is None:
+                self._cache = WeightCache()
+                self.register_weights(self._cache)
+            cache = self._cache
+            cache.refresh(dtype)
+        B, T = input_ids.shape
+        if T > self.embeddings.position_embeddings.weight.shape[0]:
+            raise ValueError(f"sequence length {T} exceeds the {self.embeddings.position_embeddings.weight.shape[0]} "
+                             "position embeddings")
+        ids = input_ids.to(torch.int64).contiguous()
+        am = attention_mask.to(device=input_ids.device, dtype=torch.float32).contiguous()
+        wT = []
+        for lyr in self.transformer.layer:
+            at = lyr.attention
+            wT.append((cache.fused_rows([at.q_lin.weight, at.k_lin.weight, at.v_lin.weight], dtype),
+                       cache.get(at.out_lin.weight, dtype), cache.get(lyr.ffn.lin1.weight, dtype),
+                       cache.get(lyr.ffn.lin2.weight, dtype)))
+        train = self.training
+        spec = Fn.TextSpec(B=B, T=T, D=self.dim, H=self.n_heads, dtype=dtype, wT=wT,
+                           p_drop=self.dropout_p if train else 0.0, p_attn=self.attn_dropout_p if train else 0.0,
+                           seed=seed, step_ptr=step_ptr, bwd_step_ptr=bwd_step_ptr, padding_idx=self.pad_token_id,
+                           grouped_wgrad=bool(CFG.wgrad_grouped), side=bool(CFG.side_stream))
+        return Fn.TextStackFn.apply(ids, am, spec, *self.stack_params())
+
     @torch.no_grad()
-    def forward(self, input_ids, attention_mask, dtype=None, seed=0, step_ptr=None):
+    def _forward_frozen(self, input_ids, attention_mask, dtype=None, seed=0, step_ptr=None):
         """Returns last_hidden_state [B, T, dim] (f32)."""
         _require_device(input_ids, "input_ids")
         dtype = dtype or compute_dtype(self.precision)
@@ -482,7 +555,8 @@ class DistilBertModel(nn.Module):
 
 
 class TextEncoder(nn.Module):
-    """modules.py:34-51: DistilBERT, frozen by default, CLS-token embedding."""
+    """modules.py:34-51: DistilBERT, frozen by default, CLS-token embedding.
+    trainable=True trains it (the reference's constructor flag, modules.py:35)."""
 
     def __init__(self, model_name=None, pretrained=False, trainable=False, n_layers=None):
         super().__init__()
@@ -490,16 +564,18 @@ class TextEncoder(nn.Module):
         if pretrained:
             raise RuntimeError("DistilBertModel.from_pretrained needs the network; construct with "
                                "pretrained=False and load a state_dict")
-        if trainable:
-            raise NotImplementedError("the text tower is forward-only (the reference freezes it, modules.py:35)")
-        self.model = DistilBertModel(n_layers=n_layers)
+        self.model = DistilBertModel(n_layers=n_layers, trainable=trainable)
         for p in self.model.parameters():
-            p.requires_grad = trainable
+            p.requires_grad = bool(trainable)
         self.target_token_idx = 0
 
-    def forward(self, input_ids, attention_mask, seed=0, dtype=None, step_ptr=None):
-        last_hidden_state = self.model(input_ids=input_ids, attention_mask=attention_mask, seed=seed, dtype=dtype,
-                                       step_ptr=step_ptr)
+    def forward(self, input_ids, attention_mask, seed=0, dtype=None, step_ptr=None, cache=None, bwd_step_ptr=None):
+        if self.model.trainable:
+            last_hidden_state = self.model(input_ids=input_ids, attention_mask=attention_mask, seed=seed, dtype=dtype,
+                                           step_ptr=step_ptr, cache=cache, bwd_step_ptr=bwd_step_ptr)
+        else:
+            last_hidden_state = self.model(input_ids=input_ids, attention_mask=attention_mask, seed=seed, dtype=dtype,
+                                           step_ptr=step_ptr)
         return last_hidden_state[:, self.target_token_idx, :]
 
 
