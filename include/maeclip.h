@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MAECLIP_ABI_VERSION 12
+#define MAECLIP_ABI_VERSION 13
 #ifndef MAECLIP_F32
 #define MAECLIP_F32 0
 #define MAECLIP_BF16 1
@@ -415,6 +415,14 @@ typedef struct {
   /* optional device step count t (>= 1): when set, step_size and bc2_sqrt are
    * recomputed in the kernel from lr, beta1, beta2 and *step_ptr */
   const int64_t* step_ptr;
+  /* ABI 13, both optional (NULL: the by-value fields above, bit for bit).
+   * lr_ptr: device learning rate, read in place of lr; decay = 1 - lr * wd and
+   * step_size = lr / (1 - beta1^t) are derived in the kernel in fp32 exactly as
+   * from the by-value lr, so it needs step_ptr. grad_scale_ptr: device factor
+   * the gradient is multiplied by in place of grad_scale (the clip coefficient
+   * of maeclip_clip_coef); the gradient tensor itself is not written. */
+  const float* lr_ptr;
+  const float* grad_scale_ptr;
 } maeclip_adamw_hparams;
 int64_t maeclip_mt_chunk(void);
 /* dev_entries: device copy of host_entries (host pointer used for the grid size) */
@@ -427,6 +435,24 @@ int32_t maeclip_cast_flat(const void* src, int32_t src_dtype, void* dst, int32_t
 /* torch.optim.AdamW step (main.py:101-103,59) fused over all parameters */
 int32_t maeclip_adamw_multi(const maeclip_mt_entry* dev_entries, const maeclip_mt_entry* host_entries, int32_t ne,
                             const maeclip_adamw_hparams* hp, void* stream);
+/* global-norm gradient clipping (ABI 13), deterministic: no atomics, every sum
+ * in a fixed order.
+ * sumsq_multi: sum of squares of the f32 tensors p1 of an AdamW plan (the other
+ * pointers are not read). Workgroup b of the plan (one per maeclip_mt_chunk()
+ * elements, as in maeclip_adamw_multi) writes partials[partial_offset + b]; the
+ * caller sizes partials for partial_offset + the plan's block count, so several
+ * plans fill disjoint ranges of one buffer.
+ * clip_coef: one workgroup sums n_partials values in double and writes
+ * norm_out[0] = sqrt(sum) and coef_out[0] = min(1, max_norm / (norm + 1e-6)),
+ * torch.nn.utils.clip_grad_norm_'s factor (NaN for a NaN norm, 0 for inf). */
+int32_t maeclip_sumsq_multi(const maeclip_mt_entry* dev_entries, const maeclip_mt_entry* host_entries, int32_t ne,
+                            float* partials, int64_t partial_offset, void* stream);
+int32_t maeclip_clip_coef(const float* partials, int64_t n_partials, float max_norm, float* norm_out, float* coef_out,
+                          void* stream);
+/* dst[i] = host_values[i], i < n <= 32 (device f32). The values are copied into
+ * the launch's kernel arguments, so host_values may be reused at once and any
+ * number of such launches may be queued (the per-group learning rates). */
+int32_t maeclip_store_f32(float* dst, const float* host_values, int32_t n, void* stream);
 
 /* ------------------------------------------------------------------- MAE */
 /* HF ViTMAE random_masking (modeling_vit_mae.py:297-327) with counter-based

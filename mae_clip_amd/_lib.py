@@ -16,7 +16,7 @@ F32, BF16 = 0, 1
 # plan options (include/maeclip.h MAECLIP_OPT_*), by name without the prefix
 OPTIONS = ("GEMM_BM", "GEMM_SK", "GEMM_SPLIT", "GEMM_SPLIT_D", "GEMM_SPLIT_MINK", "GEMM_BM128", "GEMM_GRID",
            "WG_SK", "ATTN_TWO", "ATTN_ROWS", "ATTN_DIAG", "ATTN_BW16", "ATTN_FW16")
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 c_i32, c_i64, c_f32, c_u64, c_vp, c_sz = C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_void_p, C.c_size_t
 
@@ -74,7 +74,8 @@ class ColsumEntry(C.Structure):
 
 class AdamwHparams(C.Structure):
     _fields_ = [("lr", c_f32), ("beta1", c_f32), ("beta2", c_f32), ("eps", c_f32), ("weight_decay", c_f32),
-                ("step_size", c_f32), ("bc2_sqrt", c_f32), ("grad_scale", c_f32), ("step_ptr", c_vp)]
+                ("step_size", c_f32), ("bc2_sqrt", c_f32), ("grad_scale", c_f32), ("step_ptr", c_vp),
+                ("lr_ptr", c_vp), ("grad_scale_ptr", c_vp)]
 
 
 class MaskArgs(C.Structure):
@@ -189,6 +190,9 @@ _SIGS = {
     "maeclip_colsum_multi": (c_i32, [c_vp, C.POINTER(ColsumEntry), c_i32, c_vp]),
     "maeclip_cast_multi": (c_i32, [c_vp, C.POINTER(MtEntry), c_i32, c_vp]),
     "maeclip_adamw_multi": (c_i32, [c_vp, C.POINTER(MtEntry), c_i32, C.POINTER(AdamwHparams), c_vp]),
+    "maeclip_sumsq_multi": (c_i32, [c_vp, C.POINTER(MtEntry), c_i32, c_vp, c_i64, c_vp]),
+    "maeclip_clip_coef": (c_i32, [c_vp, c_i64, c_f32, c_vp, c_vp, c_vp]),
+    "maeclip_store_f32": (c_i32, [c_vp, C.POINTER(c_f32), c_i32, c_vp]),
     "maeclip_mask_ids": (c_i32, [C.POINTER(MaskArgs), c_vp]),
     "maeclip_patch_gather": (c_i32, [C.POINTER(PatchArgs), c_vp]),
     "maeclip_tokens_fwd": (c_i32, [C.POINTER(TokensArgs), c_vp]),

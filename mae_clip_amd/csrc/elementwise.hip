@@ -350,16 +350,20 @@ __global__ void __launch_bounds__(NTH) adamw_multi_kernel(const maeclip_mt_entry
   float* v = (float*)e[k].p3;
   bf16_t* sh = (bf16_t*)e[k].p4;
   const int64_t n = e[k].n;
-  const float decay = 1.f - hp.lr * hp.weight_decay;
+  // device-resident lr / gradient factor (a scheduler, the clip coefficient):
+  // the same fp32 values through the same expressions as the by-value fields
+  const float lr = hp.lr_ptr ? *hp.lr_ptr : hp.lr;
+  const float gscale = hp.grad_scale_ptr ? *hp.grad_scale_ptr : hp.grad_scale;
+  const float decay = 1.f - lr * hp.weight_decay;
   const float b1 = hp.beta1, b2 = hp.beta2;
   float step_size = hp.step_size, bc2_sqrt = hp.bc2_sqrt;
   if (hp.step_ptr) {   // device step count t: bias corrections of torch's _single_tensor_adamw
     const float t = (float)*hp.step_ptr;
-    step_size = hp.lr / (1.f - powf(b1, t));
+    step_size = lr / (1.f - powf(b1, t));
     bc2_sqrt = sqrtf(1.f - powf(b2, t));
   }
   auto upd = [&](float g, float& pi, float& mi, float& vi) {
-    g *= hp.grad_scale;
+    g *= gscale;
     pi *= decay;
     mi = b1 * mi + (1.f - b1) * g;
     vi = b2 * vi + (1.f - b2) * g * g;
@@ -399,6 +403,69 @@ __global__ void __launch_bounds__(NTH) adamw_multi_kernel(const maeclip_mt_entry
     v[i] = vi;
     if (sh) sh[i] = f2bf(pi);
   }
+}
+
+// global gradient norm, pass 1: workgroup b of an AdamW plan -> partials[off + b]
+// = sum of squares of its CHUNK of the gradient p1. Fixed order (per-lane
+// accumulation in loop order, wave tree, four waves through LDS), no atomics.
+// 16-B loads when the tensor starts 16-B aligned (base is a multiple of CHUNK),
+// the last n & 3 elements by one lane each; plain (cached) loads: AdamW reads
+// the same gradients next.
+__global__ void __launch_bounds__(NTH) sumsq_multi_kernel(const maeclip_mt_entry* __restrict__ e, int ne,
+                                                          float* __restrict__ partials, int64_t off) {
+  __shared__ float red[NTH / 64];
+  const int k = find_entry(e, ne, blockIdx.x);
+  const int64_t base = (blockIdx.x - e[k].chunk_start) * CHUNK;
+  const float* gr = (const float*)e[k].p1;
+  const int64_t end = min(base + CHUNK, e[k].n);
+  float s = 0.f;
+  if ((((uintptr_t)gr) & 15) == 0) {
+    const int64_t vend = end & ~(int64_t)3;
+    for (int64_t i = base + 4 * threadIdx.x; i < vend; i += 4 * NTH) {
+      const v4f g = *(const v4f*)(gr + i);
+      s += (g[0] * g[0] + g[1] * g[1]) + (g[2] * g[2] + g[3] * g[3]);
+    }
+    const int64_t j = vend + threadIdx.x;
+    if (j < end) s += gr[j] * gr[j];
+  } else {
+    for (int64_t i = base + threadIdx.x; i < end; i += NTH) s += gr[i] * gr[i];
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[off + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// pass 2: one workgroup of CC_NTH lanes (the ~21 k partials of a ViT-B step are
+// latency-bound loads: 16 waves keep more of them in flight), partials summed in
+// double in a fixed order (strided per-lane sums, then a binary tree through LDS)
+constexpr int CC_NTH = 1024;
+__global__ void __launch_bounds__(CC_NTH) clip_coef_kernel(const float* __restrict__ partials, int64_t n,
+                                                           float max_norm, float* __restrict__ norm_out,
+                                                           float* __restrict__ coef_out) {
+  __shared__ double red[CC_NTH];
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += CC_NTH) s += (double)partials[i];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = CC_NTH / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt(red[0]);
+    const float c = max_norm / (norm + 1e-6f);
+    norm_out[0] = norm;
+    coef_out[0] = c > 1.f ? 1.f : c;   // torch.clamp(c, max=1): a NaN norm stays NaN
+  }
+}
+
+// a few host floats, carried in the kernel arguments, to device memory
+struct store_vals {
+  float v[32];
+};
+__global__ void store_f32_kernel(float* __restrict__ dst, store_vals vals, int n) {
+  if ((int)threadIdx.x < n) dst[threadIdx.x] = vals.v[threadIdx.x];
 }
 
 int64_t mt_blocks(const maeclip_mt_entry* host_entries, int ne) {
@@ -564,10 +631,45 @@ extern "C" int32_t maeclip_cast_multi(const maeclip_mt_entry* dev_entries, const
 extern "C" int32_t maeclip_adamw_multi(const maeclip_mt_entry* dev_entries, const maeclip_mt_entry* host_entries,
                                        int32_t ne, const maeclip_adamw_hparams* hp, void* stream) {
   MC_CHECK_ARG(dev_entries && host_entries && hp && ne > 0, "maeclip_adamw_multi: bad args");
+  MC_CHECK_ARG(!hp->lr_ptr || hp->step_ptr, "maeclip_adamw_multi: lr_ptr needs step_ptr");
   const int64_t nb = mt_blocks(host_entries, ne);
   if (nb == 0) return 0;
   hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)nb), dim3(NTH), 0, (hipStream_t)stream, dev_entries, ne, *hp);
   MC_CHECK_LAUNCH("maeclip_adamw_multi");
+  return 0;
+}
+
+extern "C" int32_t maeclip_sumsq_multi(const maeclip_mt_entry* dev_entries, const maeclip_mt_entry* host_entries,
+                                       int32_t ne, float* partials, int64_t partial_offset, void* stream) {
+  MC_CHECK_ARG(dev_entries && host_entries && partials, "maeclip_sumsq_multi: null pointer");
+  MC_CHECK_ARG(ne > 0 && partial_offset >= 0, "maeclip_sumsq_multi: ne %d, partial_offset %lld", (int)ne,
+               (long long)partial_offset);
+  const int64_t nb = mt_blocks(host_entries, ne);
+  if (nb == 0) return 0;
+  hipLaunchKernelGGL(sumsq_multi_kernel, dim3((unsigned)nb), dim3(NTH), 0, (hipStream_t)stream, dev_entries, ne,
+                     partials, partial_offset);
+  MC_CHECK_LAUNCH("maeclip_sumsq_multi");
+  return 0;
+}
+
+extern "C" int32_t maeclip_clip_coef(const float* partials, int64_t n_partials, float max_norm, float* norm_out,
+                                     float* coef_out, void* stream) {
+  MC_CHECK_ARG(partials && norm_out && coef_out, "maeclip_clip_coef: null pointer");
+  MC_CHECK_ARG(n_partials > 0, "maeclip_clip_coef: n_partials %lld", (long long)n_partials);
+  MC_CHECK_ARG(max_norm > 0.f, "maeclip_clip_coef: max_norm %g must be > 0", (double)max_norm);
+  hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(CC_NTH), 0, (hipStream_t)stream, partials, n_partials, max_norm,
+                     norm_out, coef_out);
+  MC_CHECK_LAUNCH("maeclip_clip_coef");
+  return 0;
+}
+
+extern "C" int32_t maeclip_store_f32(float* dst, const float* host_values, int32_t n, void* stream) {
+  MC_CHECK_ARG(dst && host_values, "maeclip_store_f32: null pointer");
+  MC_CHECK_ARG(n > 0 && n <= 32, "maeclip_store_f32: n %d not in 1..32", (int)n);
+  store_vals vals = {};
+  for (int i = 0; i < n; ++i) vals.v[i] = host_values[i];
+  hipLaunchKernelGGL(store_f32_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, dst, vals, (int)n);
+  MC_CHECK_LAUNCH("maeclip_store_f32");
   return 0;
 }
 

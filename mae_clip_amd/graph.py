@@ -75,8 +75,15 @@ class CapturedStep:
         self.calls = 0
 
     def _hparams(self):
-        """Optimizer hyper-parameters baked into the captured AdamW launch."""
-        return tuple((g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"]) for g in self.opt.param_groups)
+        """Optimizer hyper-parameters baked into the captured AdamW launch. An
+        optimizer with device_lr reads lr from device memory (optim.AdamW.push_lr
+        keeps it current), so lr is no part of its graph."""
+        dev_lr = self._device_lr()
+        return tuple((None if dev_lr else g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"])
+                     for g in self.opt.param_groups)
+
+    def _device_lr(self):
+        return bool(getattr(self.opt, "device_lr", False))
 
     def _publish(self, loss):
         """write the loss into pinned, device-mapped host memory from inside the
@@ -145,6 +152,8 @@ class CapturedStep:
         model_step = self.model.step
         # grads are re-created inside the graph's private pool: drop the eager ones
         self.opt.zero_grad(set_to_none=True)
+        if self._device_lr():
+            self.opt.push_lr()   # on the replay stream, never inside the capture
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         # backward seed allocated outside the graph: loss.backward() would fill
@@ -194,7 +203,11 @@ class CapturedStep:
         A batch whose shapes differ from the captured ones (e.g. the last,
         partial batch of an epoch: the reference's DataLoader keeps it,
         main.py:42-47) runs as an eager step; a change of lr / betas / eps /
-        weight_decay (e.g. by a scheduler, main.py:104) re-captures the graph."""
+        weight_decay (e.g. by a scheduler, main.py:104) re-captures the graph.
+        With optim.AdamW(device_lr=True) the learning rate lives on the device:
+        a change of lr (a per-batch scheduler) is pushed there before the replay
+        (one small launch, none when unchanged) and the one graph is kept;
+        betas / eps / weight_decay still re-capture."""
         if self.graph is not None and self._state_key() != self.state_key:
             self.invalidate()   # parameters / optimizer state changed outside the graph
         self.calls += 1
@@ -213,6 +226,8 @@ class CapturedStep:
             for k, v in batch.items():
                 if v.data_ptr() != self.static[k].data_ptr():
                     self.static[k].copy_(v, non_blocking=True)
+        if self._device_lr():
+            self.opt.push_lr()
         self.graph.replay()
         self.model.step += 1
         self.opt._advance_host_steps(1)

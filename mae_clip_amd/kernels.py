@@ -1007,10 +1007,60 @@ def cast_multi(plan: MultiTensorPlan):
     _call("maeclip_cast_multi", plan.dev.data_ptr(), plan.host, plan.n, _stream())
 
 
-def adamw_multi(plan: MultiTensorPlan, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, step_ptr=None):
-    """step: host step count t (>= 1), or step_ptr: device int64 holding t."""
+def adamw_multi(plan: MultiTensorPlan, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, step_ptr=None,
+                lr_ptr=None, grad_scale_ptr=None):
+    """step: host step count t (>= 1), or step_ptr: device int64 holding t.
+    lr_ptr / grad_scale_ptr: device f32 scalars read in place of lr / grad_scale
+    (lr_ptr needs step_ptr: the kernel derives the step size from both)."""
     bc1 = 1.0 - beta1 ** max(step, 1)
     bc2 = 1.0 - beta2 ** max(step, 1)
+    _dev(lr_ptr, grad_scale_ptr)
+    for t in (lr_ptr, grad_scale_ptr):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError("adamw_multi: lr_ptr / grad_scale_ptr are f32 device tensors")
     hp = L.AdamwHparams(lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, step_size=lr / bc1,
-                        bc2_sqrt=bc2 ** 0.5, grad_scale=grad_scale, step_ptr=_ptr(step_ptr))
+                        bc2_sqrt=bc2 ** 0.5, grad_scale=grad_scale, step_ptr=_ptr(step_ptr), lr_ptr=_ptr(lr_ptr),
+                        grad_scale_ptr=_ptr(grad_scale_ptr))
     _call("maeclip_adamw_multi", plan.dev.data_ptr(), plan.host, plan.n, C.byref(hp), _stream())
+
+
+def mt_blocks(plan: MultiTensorPlan) -> int:
+    """Workgroups (one per maeclip_mt_chunk() elements) of a multi-tensor plan."""
+    chunk = int(L.lib().maeclip_mt_chunk())
+    last = plan.host[plan.n - 1]
+    return int(last.chunk_start) + (int(last.n) + chunk - 1) // chunk
+
+
+def sumsq_multi(plan: MultiTensorPlan, partials, offset=0):
+    """partials[offset + b] = sum of squares of workgroup b's chunk of the plan's
+    gradients (p1); returns the number of partials written (the block count)."""
+    _dev(partials)
+    nb = mt_blocks(plan)
+    if partials.dtype != torch.float32 or not partials.is_contiguous() or offset < 0 \
+            or partials.numel() < offset + nb:
+        raise ValueError(f"sumsq_multi: partials must be a dense f32 tensor of >= {offset + nb} values")
+    _call("maeclip_sumsq_multi", plan.dev.data_ptr(), plan.host, plan.n, partials.data_ptr(), int(offset), _stream())
+    return nb
+
+
+def clip_coef(partials, n_partials, max_norm, norm_out, coef_out):
+    """norm_out[0] = sqrt(sum(partials[:n_partials])), coef_out[0] = min(1,
+    max_norm / (norm + 1e-6)): the factor of torch.nn.utils.clip_grad_norm_."""
+    _dev(partials, norm_out, coef_out)
+    for t in (partials, norm_out, coef_out):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise TypeError("clip_coef: dense f32 device tensors")
+    if not 0 < n_partials <= partials.numel() or norm_out.numel() < 1 or coef_out.numel() < 1:
+        raise ValueError("clip_coef: n_partials outside the partials buffer, or an empty output")
+    _call("maeclip_clip_coef", partials.data_ptr(), int(n_partials), float(max_norm), norm_out.data_ptr(),
+          coef_out.data_ptr(), _stream())
+
+
+def store_f32(dst, values):
+    """dst[:len(values)] = values (<= 32 Python floats -> device f32). The values
+    travel in the launch's arguments: nothing on the host has to outlive the call."""
+    _dev(dst)
+    n = len(values)
+    if dst.dtype != torch.float32 or not dst.is_contiguous() or not 0 < n <= min(32, dst.numel()):
+        raise ValueError("store_f32: 1..32 values into a dense f32 tensor that holds them")
+    _call("maeclip_store_f32", dst.data_ptr(), (L.c_f32 * n)(*values), n, _stream())

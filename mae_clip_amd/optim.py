@@ -9,6 +9,26 @@ optimizer step can be captured into a HIP graph together with the forward and
 backward (mae_clip_amd.graph.CapturedStep). The per-parameter host
 state["step"] is kept equal to it (state_dict / load_state_dict compatible
 with torch.optim.AdamW).
+
+Two options, both off by default, keep a normal training recipe inside one
+captured graph:
+
+device_lr=True   one device f32 array holds the learning rate of every
+                 parameter group and the AdamW launch reads its group's slot.
+                 group["lr"] stays the Python float schedulers, state_dict and
+                 get_last_lr see; push_lr() sends it to the device when it
+                 changed. Same fp32 value, same kernel arithmetic: bit-identical
+                 to the by-value path.
+max_grad_norm=c  torch.nn.utils.clip_grad_norm_(params, c) fused into the step:
+                 a deterministic global norm over every parameter of every
+                 group that has a gradient (two launches per step plus one per
+                 group), and the AdamW kernel multiplies the gradient it reads
+                 by min(1, c / (norm + 1e-6)). Unlike clip_grad_norm_, p.grad
+                 itself is NOT rescaled. `grad_norm` and `clip_coef` are device
+                 f32 [1] tensors refreshed by every step (stable storage).
+                 Under data parallelism step() runs after sync_gradients(), so
+                 every rank computes the same coefficient from the same reduced
+                 gradients: no collective is added.
 """
 from __future__ import annotations
 
@@ -18,14 +38,27 @@ from . import kernels as K
 from . import _lib as L
 from .modules import shadow_of
 
+_STORE_MAX = 32   # values of one maeclip_store_f32 launch
+
 
 class AdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None,
+                 device_lr=False):
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"max_grad_norm must be > 0 or None, got {max_grad_norm}")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         self._stager = K.PinnedStager(slots=2)
         self._step_dev = None     # device int64[1]: step count t of the uniform-step path
         self._dev_mirror = 0      # host copy of the value *_step_dev will hold when the stream gets there
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.device_lr = bool(device_lr)
+        self._lr_dev = None       # device f32[len(param_groups)]
+        self._lr_mirror = None    # the values the stream's last store wrote there
+        self.grad_norm = None     # device f32[1]: global gradient norm of the last step
+        self.clip_coef = None     # device f32[1]: factor the last step applied to the gradients
+        self._partials = None     # device f32: per-workgroup sums of squares
+        self._retired = []
 
     def _plan(self, entries, device):
         """Entry array staged through the pinned stager (async H2D, capturable)."""
@@ -52,15 +85,66 @@ class AdamW(torch.optim.Optimizer):
         self._dev_mirror = t
         return self._step_dev
 
+    def push_lr(self):
+        """device_lr: write every group["lr"] into the device array when one of
+        them differs from what the stream last stored there (one launch per 32
+        groups, none when nothing changed). Never call it on a capturing stream:
+        a store captured into a graph would reset the rate on every replay.
+        graph.CapturedStep calls it before each capture and replay."""
+        if not self.device_lr:
+            return
+        lrs = [float(g["lr"]) for g in self.param_groups]
+        device = next((p.device for g in self.param_groups for p in g["params"]), None)
+        if device is None:
+            return
+        if self._lr_dev is None or self._lr_dev.numel() != len(lrs) or self._lr_dev.device != device:
+            if K._capturing():
+                raise L.MaeClipNativeError("AdamW(device_lr=True): run one eager step (or push_lr()) before a capture")
+            self._lr_dev = torch.zeros(len(lrs), dtype=torch.float32, device=device)
+            self._lr_mirror = None
+        if lrs == self._lr_mirror:
+            return
+        if K._capturing():
+            raise L.MaeClipNativeError("AdamW.push_lr() on a capturing stream: the rate would be baked into the graph")
+        for i in range(0, len(lrs), _STORE_MAX):
+            K.store_f32(self._lr_dev[i:i + _STORE_MAX], lrs[i:i + _STORE_MAX])
+        self._lr_mirror = lrs
+
+    def _clip(self, plans, device):
+        """Global gradient norm over `plans` and the clip coefficient (device)."""
+        need = sum(K.mt_blocks(pl) for pl in plans)
+        if self._partials is None or self._partials.numel() < need or self._partials.device != device:
+            if K._capturing():
+                raise L.MaeClipNativeError(
+                    "AdamW(max_grad_norm): clip buffers first needed inside a graph capture; run the step eagerly first")
+            # an outgrown buffer is kept alive: a captured graph may still address it
+            if self._partials is not None:
+                self._retired.append(self._partials)
+            self._partials = torch.zeros(need, dtype=torch.float32, device=device)
+            if self.grad_norm is None or self.grad_norm.device != device:
+                self.grad_norm = torch.zeros(1, dtype=torch.float32, device=device)
+                self.clip_coef = torch.ones(1, dtype=torch.float32, device=device)
+        off = 0
+        for pl in plans:
+            off += K.sumsq_multi(pl, self._partials, off)
+        K.clip_coef(self._partials, off, self.max_grad_norm, self.grad_norm, self.clip_coef)
+        return self.clip_coef
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        for group in self.param_groups:
+        if self.device_lr:
+            if not K._capturing():
+                self.push_lr()
+            elif self._lr_dev is None:
+                raise L.MaeClipNativeError("AdamW(device_lr=True): run one eager step (or push_lr()) before a capture")
+        work = []     # (group index, plan, step count t, t is uniform over the group)
+        device = None
+        for gi, group in enumerate(self.param_groups):
             entries = []
-            device = None
             for p in group["params"]:
                 if p.grad is None:
                     continue
@@ -80,18 +164,30 @@ class AdamW(torch.optim.Optimizer):
                 device = p.device
             if not entries:
                 continue
-            b1, b2 = group["betas"]
             steps = sorted({e[6] for e in entries})
             if len(steps) == 1:
                 # every parameter at the same t (the training loop's case): t on the device
-                t = steps[0]
-                plan = self._plan([e[:6] for e in entries], device)
-                K.adamw_multi(plan, group["lr"], b1, b2, group["eps"], group["weight_decay"], t,
-                              step_ptr=self._device_step(t, device))
+                work.append((gi, self._plan([e[:6] for e in entries], device), steps[0], True))
             else:
                 for s in steps:
-                    plan = self._plan([e[:6] for e in entries if e[6] == s], device)
-                    K.adamw_multi(plan, group["lr"], b1, b2, group["eps"], group["weight_decay"], s)
+                    work.append((gi, self._plan([e[:6] for e in entries if e[6] == s], device), s, False))
+        if not work:
+            return loss
+        # the norm is global (clip_grad_norm_(model.parameters())): every group's
+        # gradients are summed before the first update
+        coef = self._clip([w[1] for w in work], device) if self.max_grad_norm is not None else None
+        for gi, plan, t, uniform in work:
+            group = self.param_groups[gi]
+            b1, b2 = group["betas"]
+            lr_ptr = self._lr_dev[gi:gi + 1] if self.device_lr else None
+            if uniform:
+                step_ptr = self._device_step(t, device)
+            else:
+                # mixed step counts (parameters that joined later): t by value, or,
+                # for the kernel to pair it with the device lr, in a device scalar
+                step_ptr = torch.full((1,), t, dtype=torch.int64, device=device) if self.device_lr else None
+            K.adamw_multi(plan, group["lr"], b1, b2, group["eps"], group["weight_decay"], t, step_ptr=step_ptr,
+                          lr_ptr=lr_ptr, grad_scale_ptr=coef)
         return loss
 
     def _advance_host_steps(self, delta):
