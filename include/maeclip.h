@@ -425,7 +425,13 @@ typedef struct {
   const float* grad_scale_ptr;
 } maeclip_adamw_hparams;
 int64_t maeclip_mt_chunk(void);
-/* dev_entries: device copy of host_entries (host pointer used for the grid size) */
+/* dev_entries: device copy of host_entries (host pointer used for the grid size).
+ * cast_multi: p4[i] = bf16(p0[i]) (RNE, NaN stays NaN), i < n, per entry. No
+ * alignment contract beyond the element types' own (4 B for p0, 2 B for p4):
+ * an entry whose p0 is 16-B aligned, whose p4 is 8-B aligned and whose n is a
+ * multiple of 4 is converted with 16-B loads and 8-B stores, any other entry
+ * element by element, with the same result. maeclip_adamw_multi makes the same
+ * per-entry choice (p0..p3 16-B aligned, p4 8-B aligned, n % 4 == 0). */
 int32_t maeclip_cast_multi(const maeclip_mt_entry* dev_entries, const maeclip_mt_entry* host_entries, int32_t ne,
                            void* stream);
 /* flat conversion dst[i] = scale * src[i], dtypes MAECLIP_F32 / MAECLIP_BF16

@@ -315,13 +315,15 @@ __global__ void __launch_bounds__(NTH) cast_multi_kernel(const maeclip_mt_entry*
   const float* src = (const float*)e[k].p0;
   bf16_t* dst = (bf16_t*)e[k].p4;
   const int64_t n = e[k].n;
-  for (int64_t i = base + threadIdx.x * 4; i < base + CHUNK && i < n; i += NTH * 4) {
-    if (i + 3 < n) {
+  // 16-B loads / 8-B stores only when the entry allows (the test of the AdamW
+  // kernel below): base is a multiple of CHUNK, so the entry's own alignment decides
+  const bool vec = (n & 3) == 0 && (((uintptr_t)src) & 15) == 0 && (((uintptr_t)dst) & 7) == 0;
+  if (vec) {
+    for (int64_t i = base + threadIdx.x * 4; i < base + CHUNK && i < n; i += NTH * 4)
       st4<bf16_t>(dst + i, *(const v4f*)(src + i));
-    } else {
-      for (int64_t j = i; j < n; ++j) dst[j] = f2bf(src[j]);
-    }
+    return;
   }
+  for (int64_t i = base + threadIdx.x; i < base + CHUNK && i < n; i += NTH) dst[i] = f2bf(src[i]);
 }
 
 // flat dtype conversion dst = scale * src (f32 <-> bf16, RNE): the bf16
