@@ -27,10 +27,6 @@ import torch
 from . import kernels as K
 
 
-def _reduce(part, out=None):
-    return K.colsum_reduce(part, out=out)
-
-
 # --------------------------------------------------------- gradient arena
 # Data parallel (mae_clip_amd.distributed.DataParallel) keeps every trainable
 # gradient in ONE flat fp32 buffer; the backward of each Function below writes
@@ -287,7 +283,6 @@ def microbatch_count(spec) -> int:
     64-row groups of the GEMM column-sum partials (and of the fp8 blocks'
     scale layout)."""
     from . import config as CFG
-    import os
     S = int(getattr(CFG, "stack_microbatches", 1) or 1)
     # A/B scans only: MAECLIP_MB_D<width> overrides the count for stacks of that width
     S = int(os.environ.get(f"MAECLIP_MB_D{spec.D}", S))
@@ -296,225 +291,254 @@ def microbatch_count(spec) -> int:
     return S if (spec.B // S * spec.n) % 64 == 0 else 1
 
 
+def _f8(spec, i):
+    """block i's fp8 weight operands ((W, W^T) x (qkv, proj, fc1, fc2)); Nones outside fp8 mode"""
+    return spec.w8[i] if spec.w8 is not None else (None,) * 4
+
+
+def _dst(d, name, shape, dtype, dev):
+    """destination `name` of d, else a new tensor (for the outputs a kernel
+    wrapper does not allocate itself)"""
+    t = d.get(name)
+    return t if t is not None else torch.empty(shape, device=dev, dtype=dtype)
+
+
+def _noop(*a):
+    pass
+
+
+def block_forward(spec, w, p, f8, x, Bs, d={}, tick=_noop):
+    """The 7 forward launches of one pre-LN block (LN, qkv, attention,
+    proj + residual, LN, fc1 + GELU', fc2 + residual) on the rows x [Bs * n, D]
+    of Bs whole samples, on the current stream. w: the block's (qkv, proj, fc1,
+    fc2) weights in spec.dtype, p: its PER_BLOCK parameters, f8: _f8(spec, i).
+    d: destinations by name (h1 m1 r1 qkv o lse x1 h2 m2 r2 dgelu a x2), e.g.
+    row slices of whole-batch buffers; an output without one is a new tensor.
+    tick() is called between launches. Returns (the tensors the backward
+    needs, by name; the block's output x2)."""
+    wqkv, wproj, w1, w2 = w
+    n1w, n1b, _, bqkv, _, bproj, n2w, n2b, _, b1, _, b2 = p
+    n, D, H, T = spec.n, spec.D, spec.H, spec.dtype
+    hd = D // H
+    M, F, dev = Bs * n, w1.shape[0], x.device
+    q1 = _q8(f8[0], M, D, K.FP8_E4M3, dev)
+    h1, m1, r1, _, _ = K.ln_fwd(x, n1w, n1b, spec.eps, out_dtype=T, q8=q1, y_out=d.get("h1"), mean_out=d.get("m1"),
+                                rstd_out=d.get("r1"))
+    tick()
+    qkv = _fwd(h1, wqkv, f8[0], xq=q1, bias=bqkv, out=d.get("qkv"))
+    del q1
+    tick()
+    o8 = _attn_q8(f8[1], M, D, K.FP8_E4M3, dev, False)   # the proj GEMM's fp8 operand
+    o, lse = K.attn_fwd(qkv, Bs, n, H, hd, hd ** -0.5, q8=o8, o_out=d.get("o"), lse_out=d.get("lse"))
+    tick()
+    x1 = _fwd(o, wproj, f8[1], xq=o8, bias=bproj, out_dtype=torch.float32, epilogue=K.EPI_RESID, resid=x,
+              out=d.get("x1"))
+    del o8
+    tick()
+    q2 = _q8(f8[2], M, D, K.FP8_E4M3, dev)
+    h2, m2, r2, _, _ = K.ln_fwd(x1, n2w, n2b, spec.eps, out_dtype=T, q8=q2, y_out=d.get("h2"), mean_out=d.get("m2"),
+                                rstd_out=d.get("r2"))
+    tick()
+    # fc1 epilogue: a = gelu(h), dgelu = gelu'(h) saved for the backward
+    # (+ a's fp8 blocks for fc2 in fp8 mode)
+    dgelu = _dst(d, "dgelu", (M, F), T, dev)
+    a8 = _b8(f8[3], M, F, K.FP8_E4M3, dev)
+    a = _fwd(h2, w1, f8[2], xq=q2, q8=a8, bias=b1, epilogue=K.EPI_GELU_D, aux_out=dgelu, out=d.get("a"))
+    del q2
+    tick()
+    x2 = _fwd(a, w2, f8[3], xq=a8, bias=b2, out_dtype=torch.float32, epilogue=K.EPI_RESID, resid=x1, out=d.get("x2"))
+    return dict(x=x, h1=h1, m1=m1, r1=r1, qkv=qkv, o=o, lse=lse, x1=x1, h2=h2, m2=m2, r2=r2, dgelu=dgelu, a=a), x2
+
+
+def block_backward(spec, w, p, f8, f8n, t, Bs, d={}, after=_noop):
+    """The 7 backward launches of one block (fc2 dgrad x GELU', fc1 dgrad, LN,
+    proj dgrad, attention, qkv dgrad, LN) on the rows of Bs whole samples, on
+    the current stream. t: the block's tensors of these rows by name -- the
+    forward's (block_forward) and the residual-stream gradient from above: g
+    (f32), gT (its copy in spec.dtype) and gq (gT's fp8 rows, fp8 mode). The
+    outputs are added to t under the names _GRADS books them by; dx, dxT, gq
+    and pc1 are the block below's g, gT, gq and column partials. f8n: the fc2
+    operand of the block below (its dgrad reads dxT). d: destinations by name;
+    after(k) is called between launch k and launch k + 1 (the gradients _GRADS
+    lists for launch k can be booked from t there)."""
+    wqkv, wproj, w1, w2 = w
+    n1w, n2w = p[0], p[6]
+    n, D, H = spec.n, spec.D, spec.H
+    hd = D // H
+    scale = hd ** -0.5
+    bf = spec.dtype == torch.bfloat16
+    M, F, dev = Bs * n, w1.shape[0], t["g"].device
+    gq = t.pop("gq")
+    # mlp.fc2 (+ GELU backward fused into the dgrad epilogue: dA = (dy W2) * gelu'(h))
+    t["dA_part"] = _dst(d, "dA_part", (K.gemm_colsum_rows(M), F), torch.float32, dev)
+    dA8 = _b8(f8[2], M, F, _gfmt(), dev)   # fc1's dgrad operand (fp8 mode)
+    t["dA"] = _dgrad(t["gT"], w2, f8[3], dyq=gq, q8=dA8, epilogue=K.EPI_MUL_AUX, aux=t["dgelu"], colsum=t["dA_part"],
+                     out=d.get("dA"))
+    del gq
+    after(0)
+    # mlp.fc1
+    dh2 = _dgrad(t["dA"], w1, f8[2], dyq=dA8, out=d.get("dh2"))
+    del dA8
+    after(1)
+    del t["dA"]
+    # norm2 (+ residual gradient)
+    q1 = _q8(f8[1], M, D, _gfmt(), dev)
+    dx1, dx1T, t["pg2"], t["pb2"], t["pc2"] = K.ln_bwd(
+        dh2, t["x1"], t["m2"], t["r2"], n2w, dres=t["g"], want_bf16=bf, want_colsum=True, q8=q1, dx_out=d.get("dx1"),
+        dxb_out=d.get("dx1T"), pg_out=d.get("pg2"), pb_out=d.get("pb2"), pc_out=d.get("pc2"))
+    t["dx1T"] = dx1T if bf else dx1
+    after(2)
+    # attn.proj
+    dO = _dgrad(t["dx1T"], wproj, f8[1], dyq=q1, out=d.get("dO"))
+    del q1
+    after(3)
+    # attention
+    dq8 = _attn_q8(f8[0], M, 3 * D, _gfmt(), dev, True)   # the qkv dgrad's fp8 operand
+    t["dqkv"], t["qpart"] = K.attn_bwd(t["qkv"], t["o"], dO, t["lse"], Bs, n, H, hd, scale, dqkv_out=d.get("dqkv"),
+                                       part_out=d.get("qpart"), q8=dq8)
+    del dO
+    after(4)
+    dh1 = _dgrad(t["dqkv"], wqkv, f8[0], dyq=dq8, out=d.get("dh1"))
+    del dq8
+    after(5)
+    del t["dqkv"]
+    # norm1 (+ residual gradient); the fc2 dgrad of the block below reads dxT:
+    # quantised here when it is fp8
+    t["gq"] = _q8(f8n, M, D, _gfmt(), dev)
+    t["dx"], dxT, t["pg1"], t["pb1"], t["pc1"] = K.ln_bwd(
+        dh1, t["x"], t["m1"], t["r1"], n1w, dres=dx1, want_bf16=bf, want_colsum=True, q8=t["gq"], dx_out=d.get("dx"),
+        dxb_out=d.get("dxT"), pg_out=d.get("pg1"), pb_out=d.get("pb1"), pc_out=d.get("pc1"))
+    t["dxT"] = dxT if bf else t["dx"]
+
+
+# The 12 parameter gradients of a block in booking order: (the backward launch
+# that completes the inputs, index in the block's parameters, inputs by their
+# block_backward names). One input: the column partials of a bias / LayerNorm
+# gradient (K.ReduceBatch); two: dy and x of a weight gradient dy^T x
+# (WgradQueue). cpart: the column partials of the gradient from above.
+_GRADS = ((0, 11, "cpart"), (0, 10, "gT", "a"), (0, 9, "dA_part"), (1, 8, "dA", "h2"), (2, 6, "pg2"), (2, 7, "pb2"),
+          (2, 5, "pc2"), (3, 4, "dx1T", "o"), (4, 3, "qpart"), (5, 2, "dqkv", "h1"), (6, 0, "pg1"), (6, 1, "pb1"))
+
+
+def _book(gi, rb, wq, arena, p, t, launch=None):
+    """Queues the gradients of a block's parameters p whose inputs launch
+    `launch` of block_backward completed (None: all 12) from the block's
+    tensors t; gi: the block's PER_BLOCK slots of the stack's gradient list."""
+    for k, j, *names in _GRADS:
+        if launch is None or k == launch:
+            ins = [t[nm] for nm in names]
+            out = gout(arena, p[j])
+            gi[j] = (rb.add(ins[0], out=out) if len(ins) == 1 else wq.wgrad(ins[0], ins[1], out=out)).view(p[j].shape)
+
+
 class TransformerStackFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, spec: StackSpec, *params):
-        B, n, D, H = spec.B, spec.n, spec.D, spec.H
-        hd = D // H
-        scale = hd ** -0.5
-        T = spec.dtype
-        M = B * n
-        xi = x.reshape(M, D)
-        dev = x.device
-        S = microbatch_count(spec)
-        if S > 1:
-            return TransformerStackFn._forward_mb(ctx, xi, spec, params, S)
-        saved = []
-        for i, (wqkv, wproj, w1, w2) in enumerate(spec.wT):
-            p = params[i * PER_BLOCK:(i + 1) * PER_BLOCK]
-            n1w, n1b, _, bqkv, _, bproj, n2w, n2b, _, b1, _, b2 = p
-            f8 = spec.w8[i] if spec.w8 is not None else (None,) * 4
-            q1 = _q8(f8[0], M, D, K.FP8_E4M3, dev)
-            h1, m1, r1, _, _ = K.ln_fwd(xi, n1w, n1b, spec.eps, out_dtype=T, q8=q1)
-            qkv = _fwd(h1, wqkv, f8[0], xq=q1, bias=bqkv)
-            del q1
-            o8 = _attn_q8(f8[1], M, D, K.FP8_E4M3, dev, False)   # the proj GEMM's fp8 operand
-            o, lse = K.attn_fwd(qkv, B, n, H, hd, scale, q8=o8)
-            x1 = _fwd(o, wproj, f8[1], xq=o8, bias=bproj, out_dtype=torch.float32, epilogue=K.EPI_RESID, resid=xi)
-            del o8
-            q2 = _q8(f8[2], M, D, K.FP8_E4M3, dev)
-            h2, m2, r2, _, _ = K.ln_fwd(x1, n2w, n2b, spec.eps, out_dtype=T, q8=q2)
-            # fc1 epilogue: a = gelu(h), dgelu = gelu'(h) saved for the backward
-            # (+ a's fp8 blocks for fc2 in fp8 mode)
-            dgelu = torch.empty((M, w1.shape[0]), device=dev, dtype=T)
-            a8 = _b8(f8[3], M, w1.shape[0], K.FP8_E4M3, dev)
-            a = _fwd(h2, w1, f8[2], xq=q2, q8=a8, bias=b1, epilogue=K.EPI_GELU_D, aux_out=dgelu)
-            del q2
-            x2 = _fwd(a, w2, f8[3], xq=a8, bias=b2, out_dtype=torch.float32, epilogue=K.EPI_RESID, resid=x1)
-            del a8
-            saved.append([xi, h1, m1, r1, qkv, o, lse, x1, h2, m2, r2, dgelu, a])
-            xi = x2
-        ctx.saved = saved
-        ctx.spec = spec
-        ctx.params = params
-        ctx.arena = _arena()
-        ctx.S = 1
-        return xi.view(B, n, D)
+    """A stack of pre-LN blocks: block_forward / block_backward per block, on
+    the whole batch (S = 1: every output a new tensor, each gradient booked as
+    its inputs become ready) or on S micro-batches (MicroBatches: row slices
+    of whole-batch buffers allocated before the fork, gradients booked on the
+    whole batch after the join)."""
 
     @staticmethod
-    def _forward_mb(ctx, xi, spec, params, S):
-        B, n, D, H = spec.B, spec.n, spec.D, spec.H
-        hd = D // H
-        scale = hd ** -0.5
-        T = spec.dtype
-        M = B * n
-        dev = xi.device
-        mb = MicroBatches(B, n, S, dev)
-        e = lambda shape, dt=T: torch.empty(shape, device=dev, dtype=dt)
-        saved = []
-        # whole-batch buffers allocated on the current stream before the fork;
-        # each micro-batch writes its rows on its own stream
-        for wqkv, wproj, w1, w2 in spec.wT:
-            F = w1.shape[0]
-            saved.append([None, e((M, D)), e((M,), torch.float32), e((M,), torch.float32), e((M, 3 * D)),
-                          e((M, D)), e((B, H, n), torch.float32), e((M, D), torch.float32), e((M, D)),
-                          e((M,), torch.float32), e((M,), torch.float32), e((M, F)), e((M, F))])
-        outs = [e((M, D), torch.float32) for _ in spec.wT]
-        mb.fork()
-        xin = [xi[slice(r0, r1)] for r0, r1 in mb.rows]
-        # block by block, each micro-batch's launches on its stream in turn (the
-        # captured graph then holds S interleaved chains the replay overlaps)
-        Ms = M // S
-        for i, (wqkv, wproj, w1, w2) in enumerate(spec.wT):
-            p = params[i * PER_BLOCK:(i + 1) * PER_BLOCK]
-            n1w, n1b, _, bqkv, _, bproj, n2w, n2b, _, b1, _, b2 = p
-            _, h1, m1, r1, qkv, o, lse, x1, h2, m2, r2, dgelu, a = saved[i]
-            f8 = spec.w8[i] if spec.w8 is not None else (None,) * 4
-            for mi, rs, bs in mb.each():
-                xr = xin[mi]
-                # fp8 mode: each micro-batch's fp8 operands (LayerNorm rows, fc1's blocks)
-                q1 = _q8(f8[0], Ms, D, K.FP8_E4M3, dev)
-                K.ln_fwd(xr, n1w, n1b, spec.eps, out_dtype=T, y_out=h1[rs], mean_out=m1[rs], rstd_out=r1[rs], q8=q1)
-                mb.tick()
-                _fwd(h1[rs], wqkv, f8[0], xq=q1, bias=bqkv, out=qkv[rs])
-                mb.tick()
-                o8 = _attn_q8(f8[1], Ms, D, K.FP8_E4M3, dev, False)
-                K.attn_fwd(qkv[rs], mb.Bs, n, H, hd, scale, o_out=o[rs], lse_out=lse[bs], q8=o8)
-                mb.tick()
-                _fwd(o[rs], wproj, f8[1], xq=o8, bias=bproj, out_dtype=torch.float32, epilogue=K.EPI_RESID, resid=xr,
-                     out=x1[rs])
-                mb.tick()
-                q2 = _q8(f8[2], Ms, D, K.FP8_E4M3, dev)
-                K.ln_fwd(x1[rs], n2w, n2b, spec.eps, out_dtype=T, y_out=h2[rs], mean_out=m2[rs], rstd_out=r2[rs], q8=q2)
-                mb.tick()
-                a8 = _b8(f8[3], Ms, w1.shape[0], K.FP8_E4M3, dev)
-                _fwd(h2[rs], w1, f8[2], xq=q2, q8=a8, bias=b1, epilogue=K.EPI_GELU_D, aux_out=dgelu[rs], out=a[rs])
-                mb.tick()
-                _fwd(a[rs], w2, f8[3], xq=a8, bias=b2, out_dtype=torch.float32, epilogue=K.EPI_RESID, resid=x1[rs],
-                     out=outs[i][rs])
-                xin[mi] = outs[i][rs]
-        mb.join()
-        for i in range(len(spec.wT)):
-            saved[i][0] = xi if i == 0 else outs[i - 1]
+    def forward(ctx, x, spec: StackSpec, *params):
+        B, n, D = spec.B, spec.n, spec.D
+        xi = x.reshape(B * n, D)
+        S = microbatch_count(spec)
+        blocks = [(w, params[i * PER_BLOCK:(i + 1) * PER_BLOCK], _f8(spec, i)) for i, w in enumerate(spec.wT)]
+        if S > 1:
+            saved, xi = TransformerStackFn._forward_microbatches(spec, blocks, xi, S)
+        else:
+            saved = []
+            for w, p, f8 in blocks:
+                t, xi = block_forward(spec, w, p, f8, xi, B)
+                saved.append(t)
         ctx.saved = saved
         ctx.spec = spec
         ctx.params = params
         ctx.arena = _arena()
         ctx.S = S
-        return outs[-1].view(B, n, D)
+        return xi.view(B, n, D)
+
+    @staticmethod
+    def _forward_microbatches(spec, blocks, xi, S):
+        B, n, D, H = spec.B, spec.n, spec.D, spec.H
+        M, dev, f32 = B * n, xi.device, torch.float32
+        mb = MicroBatches(B, n, S, dev)
+        e = lambda shape, dt=spec.dtype: torch.empty(shape, device=dev, dtype=dt)
+        # whole-batch buffers allocated on the current stream before the fork;
+        # each micro-batch writes its rows on its own stream
+        saved = []
+        for (_, _, w1, _), _, _ in blocks:
+            F = w1.shape[0]
+            saved.append(dict(x=None, h1=e((M, D)), m1=e((M,), f32), r1=e((M,), f32), qkv=e((M, 3 * D)), o=e((M, D)),
+                              lse=e((B, H, n), f32), x1=e((M, D), f32), h2=e((M, D)), m2=e((M,), f32),
+                              r2=e((M,), f32), dgelu=e((M, F)), a=e((M, F))))
+        outs = [e((M, D), f32) for _ in blocks]
+        mb.fork()
+        xin = [xi[r0:r1] for r0, r1 in mb.rows]
+        # block by block, each micro-batch's launches on its stream in turn (the
+        # captured graph then holds S interleaved chains the replay overlaps)
+        for i, (w, p, f8) in enumerate(blocks):
+            for mi, rs, bs in mb.each():
+                d = {k: v[bs if k == "lse" else rs] for k, v in saved[i].items() if v is not None}
+                d["x2"] = outs[i][rs]
+                _, xin[mi] = block_forward(spec, w, p, f8, xin[mi], mb.Bs, d, mb.tick)
+        mb.join()
+        for i in range(len(blocks)):
+            saved[i]["x"] = xi if i == 0 else outs[i - 1]
+        return saved, outs[-1]
 
     @staticmethod
     def backward(ctx, gy):
-        if ctx.S > 1:
-            return TransformerStackFn._backward_mb(ctx, gy)
-        spec = ctx.spec
-        B, n, D, H = spec.B, spec.n, spec.D, spec.H
-        hd = D // H
-        scale = hd ** -0.5
-        T = spec.dtype
-        bf = T == torch.bfloat16
-        M = B * n
-        params = ctx.params
-        grads = [None] * len(params)
+        spec, params, S = ctx.spec, ctx.params, ctx.S
+        B, n, D = spec.B, spec.n, spec.D
+        bf = spec.dtype == torch.bfloat16
+        M, dev = B * n, gy.device
+        L = len(spec.wT)
+        blocks = [(spec.wT[i], params[i * PER_BLOCK:(i + 1) * PER_BLOCK], _f8(spec, i),
+                   _f8(spec, i - 1)[3] if i > 0 else None) for i in range(L)]
+        grads = [[None] * PER_BLOCK for _ in range(L)]
         rb = K.ReduceBatch()
-        wq = WgradQueue(gy.device, spec.side, spec.grouped_wgrad)
+        wq = WgradQueue(dev, spec.side, spec.grouped_wgrad)
         g = gy.reshape(M, D)
         if not g.is_contiguous():
             g = g.contiguous()
-        gT = torch.empty((M, D), device=g.device, dtype=torch.bfloat16) if bf else None
+        gT = torch.empty((M, D), device=dev, dtype=torch.bfloat16) if bf else None
         # fp8 copy of gT for the top fc2 dgrad: made with gT here (fp8 mode), then
         # by the LayerNorm backward that produces each next gT
-        gq = _q8(spec.w8[-1][3], M, D, _gfmt(), g.device) if (bf and spec.w8 is not None) else None
+        gq = _q8(blocks[-1][2][3], M, D, _gfmt(), dev)
         cpart = K.rows_colsum(g, out_bf16=gT, q8=gq)
-        if not bf:
-            gT = g
-        for i in reversed(range(len(spec.wT))):
-            wqkv, wproj, w1, w2 = spec.wT[i]
-            f8 = spec.w8[i] if spec.w8 is not None else (None,) * 4
-            p = params[i * PER_BLOCK:(i + 1) * PER_BLOCK]
-            n1w, n2w = p[0], p[6]
-            xi, h1, m1, r1, qkv, o, lse, x1, h2, m2, r2, dgelu, a = ctx.saved[i]
-            gi = [None] * PER_BLOCK
-            ar = ctx.arena
-            # mlp.fc2 (+ GELU backward fused into the dgrad epilogue: dA = (dy W2) * gelu'(h))
-            gi[11] = rb.add(cpart, out=gout(ar, p[11]))
-            dA_part = torch.empty((K.gemm_colsum_rows(M), w1.shape[0]), device=g.device, dtype=torch.float32)
-            dA8 = _b8(f8[2], M, w1.shape[0], _gfmt(), g.device)   # fc1's dgrad operand (fp8 mode)
-            dA = _dgrad(gT, w2, f8[3], dyq=gq, q8=dA8, epilogue=K.EPI_MUL_AUX, aux=dgelu, colsum=dA_part)
-            gq = None
-            gi[10] = wq.wgrad(gT, a, out=gout(ar, p[10]))
-            del a, dgelu
-            # mlp.fc1
-            gi[9] = rb.add(dA_part, out=gout(ar, p[9]))
-            dh2 = _dgrad(dA, w1, f8[2], dyq=dA8)
-            del dA8
-            gi[8] = wq.wgrad(dA, h2, out=gout(ar, p[8]))
-            del dA
-            # norm2 (+ residual gradient)
-            q1 = _q8(f8[1], M, D, _gfmt(), g.device) if bf else None
-            dx1, dx1T, pg, pb, pc = K.ln_bwd(dh2, x1, m2, r2, n2w, dres=g, want_bf16=bf, want_colsum=True, q8=q1)
-            gi[6], gi[7] = rb.add(pg, out=gout(ar, p[6])), rb.add(pb, out=gout(ar, p[7]))
-            if not bf:
-                dx1T = dx1
-            # attn.proj
-            gi[5] = rb.add(pc, out=gout(ar, p[5]))
-            dO = _dgrad(dx1T, wproj, f8[1], dyq=q1)
-            del q1
-            gi[4] = wq.wgrad(dx1T, o, out=gout(ar, p[4]))
-            # attention
-            dq8 = _attn_q8(f8[0], M, 3 * D, _gfmt(), g.device, True)   # the qkv dgrad's fp8 operand
-            dqkv, qpart = K.attn_bwd(qkv, o, dO, lse, B, n, H, hd, scale, q8=dq8)
-            del dO
-            gi[3] = rb.add(qpart, out=gout(ar, p[3]))
-            dh1 = _dgrad(dqkv, wqkv, f8[0], dyq=dq8)
-            del dq8
-            gi[2] = wq.wgrad(dqkv, h1, out=gout(ar, p[2]))
-            del dqkv
-            # norm1 (+ residual gradient)
-            # the next (lower) block's fc2 dgrad reads dxT: quantised here when it is fp8
-            f8n = (spec.w8[i - 1][3] if spec.w8 is not None and i > 0 else None)
-            gq = _q8(f8n, M, D, _gfmt(), g.device) if bf else None
-            dx, dxT, pg, pb, pc = K.ln_bwd(dh1, xi, m1, r1, n1w, dres=dx1, want_bf16=bf, want_colsum=True, q8=gq)
-            gi[0], gi[1] = rb.add(pg, out=gout(ar, p[0])), rb.add(pb, out=gout(ar, p[1]))
-            ctx.saved[i] = None
-            g, gT, cpart = dx, (dxT if bf else dx), pc
-            for j in range(PER_BLOCK):
-                grads[i * PER_BLOCK + j] = gi[j].view(p[j].shape)
-            del gi
+        up = dict(g=g, gT=gT if bf else g, gq=gq, cpart=cpart)
+        del g, gT, gq, cpart
+        if S > 1:
+            g = TransformerStackFn._backward_microbatches(ctx, blocks, up, rb, wq, grads)
+        else:
+            for i in reversed(range(L)):
+                w, p, f8, f8n = blocks[i]
+                t = dict(ctx.saved[i], **up)
+                up = None
+                block_backward(spec, w, p, f8, f8n, t, B, after=lambda k: _book(grads[i], rb, wq, ctx.arena, p, t, k))
+                _book(grads[i], rb, wq, ctx.arena, p, t, 6)
+                ctx.saved[i] = None
+                up = dict(g=t["dx"], gT=t["dxT"], gq=t["gq"], cpart=t["pc1"])
+                t = None    # the block's remaining tensors go with it
+            g = up["g"]
         rb.flush()
         wq.join()
         ctx.saved = None
-        return (g.view(B, n, D), None, *grads)
+        return (g.view(B, n, D), None, *(gj for gi in grads for gj in gi))
 
     @staticmethod
-    def _backward_mb(ctx, gy):
-        spec = ctx.spec
-        S = ctx.S
-        B, n, D, H = spec.B, spec.n, spec.D, spec.H
-        hd = D // H
-        scale = hd ** -0.5
-        T = spec.dtype
-        M = B * n
-        dev = gy.device
-        params = ctx.params
-        grads = [None] * len(params)
-        rb = K.ReduceBatch()
-        wq = WgradQueue(dev, spec.side, spec.grouped_wgrad)
+    def _backward_microbatches(ctx, blocks, up, rb, wq, grads):
+        spec, S, saved = ctx.spec, ctx.S, ctx.saved
+        B, n, D = spec.B, spec.n, spec.D
+        M, dev, f32 = B * n, up["g"].device, torch.float32
         mb = MicroBatches(B, n, S, dev)
-        e = lambda shape, dt=T: torch.empty(shape, device=dev, dtype=dt)
-        f32 = torch.float32
-        Ms = M // S
-        G = K.ln_bwd_partial_rows(Ms, D)       # LayerNorm partial rows per micro-batch
+        e = lambda shape, dt=spec.dtype: torch.empty(shape, device=dev, dtype=dt)
+        G = K.ln_bwd_partial_rows(M // S, D)    # LayerNorm partial rows per micro-batch
         GC = K.gemm_colsum_rows(M)              # GEMM column-sum partial rows (64-row groups)
-        g = gy.reshape(M, D)
-        if not g.is_contiguous():
-            g = g.contiguous()
-        gT = e((M, D))
-        gq0 = _q8(spec.w8[-1][3], M, D, _gfmt(), dev) if spec.w8 is not None else None   # top fp8 operand
-        cpart = K.rows_colsum(g, out_bf16=gT, q8=gq0)
         # whole-batch gradient buffers of every block, written per micro-batch
         bufs = []
-        for wqkv, wproj, w1, w2 in spec.wT:
+        for (_, _, w1, _), _, _, _ in blocks:
             F = w1.shape[0]
             bufs.append(dict(dA=e((M, F)), dA_part=e((GC, F), f32), dh2=e((M, D)), dx1=e((M, D), f32),
                              dx1T=e((M, D)), pg2=e((S * G, D), f32), pb2=e((S * G, D), f32),
@@ -524,68 +548,27 @@ class TransformerStackFn(torch.autograd.Function):
         mb.fork()
         # per micro-batch: (f32 residual gradient, its bf16 copy, the copy's fp8
         # rows from the LayerNorm backward that made it -- fp8 mode)
-        gin = [(g[slice(r0, r1)], gT[slice(r0, r1)],
-                None if gq0 is None else K.Fp8Rows(gq0.q[r0:r1], gq0.s[r0:r1], gq0.fmt)) for r0, r1 in mb.rows]
-        for i in reversed(range(len(spec.wT))):
-            wqkv, wproj, w1, w2 = spec.wT[i]
-            n1w, n2w = params[i * PER_BLOCK], params[i * PER_BLOCK + 6]
-            xi, h1, m1, r1, qkv, o, lse, x1, h2, m2, r2, dgelu, a = ctx.saved[i]
-            b = bufs[i]
-            f8 = spec.w8[i] if spec.w8 is not None else (None,) * 4
-            f8n = spec.w8[i - 1][3] if spec.w8 is not None and i > 0 else None
+        g, gT, gq = up["g"], up["gT"], up["gq"]
+        ups = [dict(g=g[r0:r1], gT=gT[r0:r1],
+                    gq=None if gq is None else K.Fp8Rows(gq.q[r0:r1], gq.s[r0:r1], gq.fmt)) for r0, r1 in mb.rows]
+        for i in reversed(range(len(blocks))):
+            w, p, f8, f8n = blocks[i]
             for mi, rs, bs in mb.each():
-                gs, gTs, gq = gin[mi]
-                ps = slice(mi * G, (mi + 1) * G)
-                cs = slice(rs.start // 64, rs.stop // 64)
-                dA8 = _b8(f8[2], Ms, w1.shape[0], _gfmt(), dev)
-                _dgrad(gTs, w2, f8[3], dyq=gq, q8=dA8, epilogue=K.EPI_MUL_AUX, aux=dgelu[rs],
-                       colsum=b["dA_part"][cs], out=b["dA"][rs])
-                mb.tick()
-                _dgrad(b["dA"][rs], w1, f8[2], dyq=dA8, out=b["dh2"][rs])
-                mb.tick()
-                q1 = _q8(f8[1], Ms, D, _gfmt(), dev)
-                K.ln_bwd(b["dh2"][rs], x1[rs], m2[rs], r2[rs], n2w, dres=gs, want_bf16=True, want_colsum=True,
-                         dx_out=b["dx1"][rs], dxb_out=b["dx1T"][rs], pg_out=b["pg2"][ps], pb_out=b["pb2"][ps],
-                         pc_out=b["pc2"][ps], q8=q1)
-                mb.tick()
-                _dgrad(b["dx1T"][rs], wproj, f8[1], dyq=q1, out=b["dO"][rs])
-                mb.tick()
-                dq8 = _attn_q8(f8[0], Ms, 3 * D, _gfmt(), dev, True)
-                K.attn_bwd(qkv[rs], o[rs], b["dO"][rs], lse[bs], mb.Bs, n, H, hd, scale,
-                           dqkv_out=b["dqkv"][rs], part_out=b["qpart"][bs], q8=dq8)
-                mb.tick()
-                _dgrad(b["dqkv"][rs], wqkv, f8[0], dyq=dq8, out=b["dh1"][rs])
-                mb.tick()
-                gq = _q8(f8n, Ms, D, _gfmt(), dev)
-                K.ln_bwd(b["dh1"][rs], xi[rs], m1[rs], r1[rs], n1w, dres=b["dx1"][rs], want_bf16=True,
-                         want_colsum=True, dx_out=b["dx"][rs], dxb_out=b["dxT"][rs], pg_out=b["pg1"][ps],
-                         pb_out=b["pb1"][ps], pc_out=b["pc1"][ps], q8=gq)
-                gin[mi] = (b["dx"][rs], b["dxT"][rs], gq)
+                # a micro-batch's part of each buffer: its rows, its samples (lse, the
+                # attention's bias partials), its 64-row groups, its LayerNorm partial rows
+                sel = dict.fromkeys(("pg2", "pb2", "pc2", "pg1", "pb1", "pc1"), slice(mi * G, (mi + 1) * G))
+                sel.update(lse=bs, qpart=bs, dA_part=slice(rs.start // 64, rs.stop // 64))
+                t = {k: v[sel.get(k, rs)] for k, v in saved[i].items()}
+                t.update(ups[mi])
+                d = {k: v[sel.get(k, rs)] for k, v in bufs[i].items()}
+                block_backward(spec, w, p, f8, f8n, t, mb.Bs, d, after=lambda k: mb.tick())
+                ups[mi] = dict(g=t["dx"], gT=t["dxT"], gq=t["gq"])
         mb.join()
-        ar = ctx.arena
-        for i in reversed(range(len(spec.wT))):
-            p = params[i * PER_BLOCK:(i + 1) * PER_BLOCK]
-            xi, h1, m1, r1, qkv, o, lse, x1, h2, m2, r2, dgelu, a = ctx.saved[i]
-            b = bufs[i]
-            gi = [None] * PER_BLOCK
-            gi[11] = rb.add(cpart, out=gout(ar, p[11]))
-            gi[10] = wq.wgrad(gT, a, out=gout(ar, p[10]))
-            gi[9] = rb.add(b["dA_part"], out=gout(ar, p[9]))
-            gi[8] = wq.wgrad(b["dA"], h2, out=gout(ar, p[8]))
-            gi[6], gi[7] = rb.add(b["pg2"], out=gout(ar, p[6])), rb.add(b["pb2"], out=gout(ar, p[7]))
-            gi[5] = rb.add(b["pc2"], out=gout(ar, p[5]))
-            gi[4] = wq.wgrad(b["dx1T"], o, out=gout(ar, p[4]))
-            gi[3] = rb.add(b["qpart"], out=gout(ar, p[3]))
-            gi[2] = wq.wgrad(b["dqkv"], h1, out=gout(ar, p[2]))
-            gi[0], gi[1] = rb.add(b["pg1"], out=gout(ar, p[0])), rb.add(b["pb1"], out=gout(ar, p[1]))
-            gT, cpart = b["dxT"], b["pc1"]
-            for j in range(PER_BLOCK):
-                grads[i * PER_BLOCK + j] = gi[j].view(p[j].shape)
-        rb.flush()
-        wq.join()
-        g = bufs[0]["dx"]
-        ctx.saved = None
-        return (g.view(B, n, D), None, *grads)
+        gT, cpart = up["gT"], up["cpart"]
+        for i in reversed(range(len(blocks))):
+            _book(grads[i], rb, wq, ctx.arena, blocks[i][1], dict(saved[i], **bufs[i], gT=gT, cpart=cpart))
+            gT, cpart = bufs[i]["dxT"], bufs[i]["pc1"]
+        return bufs[0]["dx"]
 
 
 # ------------------------------------------------------------ text tower
@@ -612,60 +595,85 @@ TEXT_EMB = 4        # word_embeddings, position_embeddings, LayerNorm.weight, La
 TEXT_PER_LAYER = 16  # (q, k, v, out)_lin.(weight, bias), sa_layer_norm.(w, b), lin1.(w, b), lin2.(w, b), output_layer_norm.(w, b)
 
 
+def step_snapshot(spec, dropout):
+    """The step value a backward redraws its forward's dropout masks from (None
+    when no dropout is active): the step counter advances at the end of the
+    model's forward, so the backward reads the snapshot slot the counter's
+    kernel fills (spec.bwd_step_ptr), else a copy of the counter made now."""
+    if spec.step_ptr is None or not dropout:
+        return None
+    return spec.bwd_step_ptr if spec.bwd_step_ptr is not None else spec.step_ptr.clone()
+
+
+def text_forward(ids, am, emb, layers, B, T, D, H, dt, p_drop, p_attn, seed, step_ptr, keep, eps=1e-12):
+    """The launches of HF DistilBertModel's forward (Embeddings + post-LN
+    TransformerBlocks, LN(x + sublayer(x))), shared by the frozen tower
+    (modules.DistilBertModel) and TextStackFn. emb: (word, position, LN weight,
+    LN bias); layers: per layer (q|k|v weight [3D, D] and bias, out_lin w, b,
+    sa_layer_norm w, b, lin1 w, b, lin2 w, b, output_layer_norm w, b), GEMM
+    weights in dt. am: the f32 key mask [B, T], or the tokenizer's dense int64
+    mask, converted inside the embedding launch. keep: also produce what a
+    backward needs (LayerNorm statistics and pre-norm sums, lse, gelu').
+    Returns (last_hidden_state rows [B*T, D] f32, f32 key mask, (x, mean, rstd)
+    of the embedding LayerNorm, per-layer saved tensors)."""
+    hd = D // H
+    bf = dt == torch.bfloat16
+    f32 = torch.float32
+    word, pos, eg, eb = emb
+    s0 = seed * 131
+    if am.dtype == torch.int64:
+        x, am = K.embed_fwd(ids, word, pos, mask=am)
+    else:
+        x = K.embed_fwd(ids, word, pos)
+    h, m0, r0, hT, _ = K.ln_fwd(x, eg, eb, eps, out_dtype=f32, out_dropout=p_drop, seed_out=s0 + 1, want_stats=keep,
+                                y2=bf, step_ptr=step_ptr)
+    hT = hT if bf else h
+    saved = []
+    for li, (wqkv, bqkv, wout, bout, sa_w, sa_b, w1, b1, w2, b2, out_w, out_b) in enumerate(layers):
+        qkv = K.linear_fwd(hT, wqkv, bqkv)
+        o, lse = K.attn_fwd(qkv, B, T, H, hd, hd ** -0.5, key_mask=am, dropout_p=p_attn, seed=s0 + 7 * li + 2,
+                            want_lse=keep, step_ptr=step_ptr)
+        sa = K.linear_fwd(o, wout, bout, out_dtype=f32)
+        a, m1, r1, aT, z1 = K.ln_fwd(sa, sa_w, sa_b, eps, out_dtype=f32, res=h, want_stats=keep, y2=bf, xsum=keep)
+        del sa
+        aT = aT if bf else a
+        # lin1 epilogue: f1 = gelu(.) (+ dgelu = gelu'(.) for a backward)
+        dgelu = torch.empty((B * T, w1.shape[0]), device=ids.device, dtype=dt) if keep else None
+        f1 = K.linear_fwd(aT, w1, b1, epilogue=K.EPI_GELU_D if keep else K.EPI_GELU, aux_out=dgelu)
+        f2 = K.linear_fwd(f1, w2, b2, out_dtype=f32)
+        hn, m2, r2, hnT, z2 = K.ln_fwd(f2, out_w, out_b, eps, out_dtype=f32, res=a, in_dropout=p_drop,
+                                       seed_in=s0 + 7 * li + 3, want_stats=keep, y2=bf, xsum=keep, step_ptr=step_ptr)
+        del f2, a
+        if keep:
+            saved.append([hT, qkv, o, lse, z1, m1, r1, aT, dgelu, f1, z2, m2, r2])
+        h, hT = hn, (hnT if bf else hn)
+    return h, am, (x, m0, r0), saved
+
+
 class TextStackFn(torch.autograd.Function):
-    """HF DistilBertModel (modeling_distilbert.py: Embeddings + n post-LN
-    TransformerBlocks, LN(x + sublayer(x)), eps 1e-12) as one Function:
-    last_hidden_state [B, T, D] (f32). The seeds are the frozen forward's
-    (modules.DistilBertModel); the backward redraws the three kinds of dropout
-    mask (embedding LN output, attention probabilities, FFN output) from them
-    and from the forward's step value (bwd_step_ptr, else a copy kept here)."""
+    """HF DistilBertModel (modeling_distilbert.py) as one Function:
+    last_hidden_state [B, T, D] (f32), by text_forward. The seeds are the
+    frozen forward's (modules.DistilBertModel); the backward redraws the three
+    kinds of dropout mask (embedding LN output, attention probabilities, FFN
+    output) from them and from the forward's step value (step_snapshot)."""
 
     @staticmethod
     def forward(ctx, ids, am, spec: TextSpec, *params):
-        B, T, D, H = spec.B, spec.T, spec.D, spec.H
-        hd = D // H
-        dt = spec.dtype
-        bf = dt == torch.bfloat16
-        M = B * T
-        dev = ids.device
-        word, pos, eg, eb = params[:TEXT_EMB]
-        s0 = spec.seed * 131
-        x = K.embed_fwd(ids, word, pos)
-        h, m0, r0, hT, _ = K.ln_fwd(x, eg, eb, spec.eps, out_dtype=torch.float32, out_dropout=spec.p_drop,
-                                    seed_out=s0 + 1, y2=bf, step_ptr=spec.step_ptr)
-        hT = hT if bf else h
-        saved = []
-        for li, (wqkv, wout, w1, w2) in enumerate(spec.wT):
-            p = params[TEXT_EMB + li * TEXT_PER_LAYER:TEXT_EMB + (li + 1) * TEXT_PER_LAYER]
-            bqkv = torch.cat([p[1], p[3], p[5]])
-            qkv = K.linear_fwd(hT, wqkv, bqkv)
-            o, lse = K.attn_fwd(qkv, B, T, H, hd, hd ** -0.5, key_mask=am, dropout_p=spec.p_attn,
-                                seed=s0 + 7 * li + 2, step_ptr=spec.step_ptr)
-            sa = K.linear_fwd(o, wout, p[7], out_dtype=torch.float32)
-            a, m1, r1, aT, z1 = K.ln_fwd(sa, p[8], p[9], spec.eps, out_dtype=torch.float32, res=h, y2=bf, xsum=True)
-            del sa
-            aT = aT if bf else a
-            # lin1 epilogue: f1 = gelu(.), dgelu = gelu'(.) saved for the backward
-            dgelu = torch.empty((M, w1.shape[0]), device=dev, dtype=dt)
-            f1 = K.linear_fwd(aT, w1, p[11], epilogue=K.EPI_GELU_D, aux_out=dgelu)
-            f2 = K.linear_fwd(f1, w2, p[13], out_dtype=torch.float32)
-            hn, m2, r2, hnT, z2 = K.ln_fwd(f2, p[14], p[15], spec.eps, out_dtype=torch.float32, res=a,
-                                           in_dropout=spec.p_drop, seed_in=s0 + 7 * li + 3, y2=bf, xsum=True,
-                                           step_ptr=spec.step_ptr)
-            del f2, a
-            saved.append([hT, qkv, o, lse, z1, m1, r1, aT, dgelu, f1, z2, m2, r2])
-            h, hT = hn, (hnT if bf else hn)
-        ctx.emb = (ids, am, x, m0, r0)
-        ctx.saved = saved
+        def layers():
+            # the q / k / v biases are concatenated as each layer is reached
+            for li, (wqkv, wout, w1, w2) in enumerate(spec.wT):
+                p = params[TEXT_EMB + li * TEXT_PER_LAYER:TEXT_EMB + (li + 1) * TEXT_PER_LAYER]
+                yield (wqkv, torch.cat([p[1], p[3], p[5]]), wout, p[7], p[8], p[9], w1, p[11], w2, p[13], p[14], p[15])
+
+        h, am, emb, ctx.saved = text_forward(ids, am, params[:TEXT_EMB], layers(), spec.B, spec.T, spec.D, spec.H,
+                                             spec.dtype, spec.p_drop, spec.p_attn, spec.seed, spec.step_ptr, True,
+                                             eps=spec.eps)
+        ctx.emb = (ids, am, *emb)
         ctx.spec = spec
         ctx.params = params
         ctx.arena = _arena()
-        # the step counter advances at the end of the model's forward: the
-        # backward redraws this forward's masks from a snapshot of the step
-        ctx.step_snap = None
-        if spec.step_ptr is not None and (spec.p_drop > 0 or spec.p_attn > 0):
-            ctx.step_snap = spec.bwd_step_ptr if spec.bwd_step_ptr is not None else spec.step_ptr.clone()
-        return h.view(B, T, D)
+        ctx.step_snap = step_snapshot(spec, spec.p_drop > 0 or spec.p_attn > 0)
+        return h.view(spec.B, spec.T, spec.D)
 
     @staticmethod
     def backward(ctx, gy):
@@ -802,7 +810,7 @@ class PatchTokensFn(torch.autograd.Function):
             dWo.copy_(K.linear_wgrad(dY, Xp)[:, :Kreal])
         else:
             K.linear_wgrad(dY, Xp, out=dWo)
-        db = _reduce(K.rows_colsum(dY), out=gout(ar, b))
+        db = K.colsum_reduce(K.rows_colsum(dY), out=gout(ar, b))
         return None, None, None, None, dWo.view(ctx.wshape), db, dcls.view(1, 1, D), dpos.view(1, -1, D)
 
 
@@ -836,7 +844,7 @@ class EncoderHeadFn(torch.autograd.Function):
         dpooled, _, pg, pb, _ = K.ln_bwd(gfeat.contiguous(), pooled, fm, fr, fcn_w)
         fcn_b, mn_b = ctx.b
         ar = ctx.arena
-        g_fw, g_fb = _reduce(pg, out=gout(ar, fcn_w)), _reduce(pb, out=gout(ar, fcn_b))
+        g_fw, g_fb = K.colsum_reduce(pg, out=gout(ar, fcn_w)), K.colsum_reduce(pb, out=gout(ar, fcn_b))
         g_mw = g_mb = None
         if ctx.mae and glatent is not None:
             # the avg-pool backward rides in the mae_norm LN backward as its
@@ -845,7 +853,7 @@ class EncoderHeadFn(torch.autograd.Function):
             dx2, _, pg2, pb2, _ = K.ln_bwd(glatent.contiguous(), x.view(B * n, D), lm, lr, mn_w,
                                            dres_pool=dpooled, pool_n=n)
             dx = dx2.view(B, n, D)
-            g_mw, g_mb = _reduce(pg2, out=gout(ar, mn_w)), _reduce(pb2, out=gout(ar, mn_b))
+            g_mw, g_mb = K.colsum_reduce(pg2, out=gout(ar, mn_w)), K.colsum_reduce(pb2, out=gout(ar, mn_b))
         else:
             dx = K.pool_bwd(dpooled, n)
         return dx, None, g_fw, g_fb, g_mw, g_mb
@@ -882,8 +890,8 @@ class DecoderEmbedFn(torch.autograd.Function):
         ar = ctx.arena
         dlatent = K.linear_dgrad(dy, spec.w_T)
         dW = K.linear_wgrad(dy, latent, out=gout(ar, w))
-        db = _reduce(cs, out=gout(ar, b))
-        dmask = _reduce(dmask_part, out=gout(ar, mask_token, (mask_token.shape[-1],)))
+        db = K.colsum_reduce(cs, out=gout(ar, b))
+        dmask = K.colsum_reduce(dmask_part, out=gout(ar, mask_token, (mask_token.shape[-1],)))
         return dlatent, None, None, None, dW, db, dmask.view(1, 1, -1), None
 
 
@@ -928,13 +936,13 @@ class MaeHeadLossFn(torch.autograd.Function):
         dWp = gout(ar, wp)
         if dpred.shape[1] != ctx.P:      # padded pred rows (patch 14): slice back
             dWp.copy_(K.linear_wgrad(dpred, h)[:ctx.P])
-            dbp = _reduce(cs[:, :ctx.P].contiguous() if cs.shape[1] != ctx.P else cs, out=gout(ar, bp))
+            dbp = K.colsum_reduce(cs[:, :ctx.P].contiguous() if cs.shape[1] != ctx.P else cs, out=gout(ar, bp))
         else:
             K.linear_wgrad(dpred, h, out=dWp)
-            dbp = _reduce(cs, out=gout(ar, bp))
+            dbp = K.colsum_reduce(cs, out=gout(ar, bp))
         dx, _, pg, pb, _ = K.ln_bwd(dh, x2, m, r, ctx.dn_w)
-        return (dx.view(ctx.shape), None, None, None, _reduce(pg, out=gout(ar, dn_w)), _reduce(pb, out=gout(ar, dn_b)),
-                dWp, dbp)
+        return (dx.view(ctx.shape), None, None, None, K.colsum_reduce(pg, out=gout(ar, dn_w)),
+                K.colsum_reduce(pb, out=gout(ar, dn_b)), dWp, dbp)
 
 
 # --------------------------------------------------------- projection head
@@ -963,11 +971,7 @@ class ProjectionHeadFn(torch.autograd.Function):
         ctx.params = (wp, bp, wf, bf, lw, lb)
         ctx.arena = _arena()
         ctx.spec = spec
-        # the step counter advances at the end of the forward: the backward
-        # re-draws this forward's dropout mask from a snapshot of the step
-        ctx.step_snap = None
-        if spec.step_ptr is not None and spec.p_drop > 0:
-            ctx.step_snap = spec.bwd_step_ptr if spec.bwd_step_ptr is not None else spec.step_ptr.clone()
+        ctx.step_snap = step_snapshot(spec, spec.p_drop > 0)
         return out
 
     @staticmethod
@@ -980,12 +984,13 @@ class ProjectionHeadFn(torch.autograd.Function):
         dz, _, pg, pb, _ = K.ln_bwd(gout_.contiguous(), z, m, r, lw)
         df = K.dropout(dz, spec.p_drop, spec.seed, step_ptr=ctx.step_snap) if spec.p_drop > 0 else dz
         dwf = K.linear_wgrad(df, g, out=gout(ar, wf_))
-        dbf = _reduce(K.rows_colsum(df), out=gout(ar, bf_))
+        dbf = K.colsum_reduce(K.rows_colsum(df), out=gout(ar, bf_))
         dpre = K.linear_dgrad(df, wf, out_dtype=torch.float32, epilogue=K.EPI_DGELU, aux=pre, resid=dz)
         dwp = K.linear_wgrad(dpre, x, out=gout(ar, wp_))
-        dbp = _reduce(K.rows_colsum(dpre), out=gout(ar, bp_))
+        dbp = K.colsum_reduce(K.rows_colsum(dpre), out=gout(ar, bp_))
         dx = K.linear_dgrad(dpre, wp, out_dtype=torch.float32)
-        return dx, None, dwp, dbp, dwf, dbf, _reduce(pg, out=gout(ar, lw_)), _reduce(pb, out=gout(ar, lb_))
+        return (dx, None, dwp, dbp, dwf, dbf, K.colsum_reduce(pg, out=gout(ar, lw_)),
+                K.colsum_reduce(pb, out=gout(ar, lb_)))
 
 
 # ------------------------------------------------------------- CLIP loss

@@ -518,40 +518,27 @@ class DistilBertModel(nn.Module):
         _require_device(input_ids, "input_ids")
         dtype = dtype or compute_dtype(self.precision)
         B, T = input_ids.shape
-        D, H = self.dim, self.n_heads
-        hd = D // H
         train = self.training
-        pdrop = self.dropout_p if train else 0.0
-        padrop = self.attn_dropout_p if train else 0.0
-        bf = dtype == torch.bfloat16
         ids = input_ids.to(torch.int64).contiguous()
+        am = attention_mask
+        if not (am.dtype == torch.int64 and am.is_contiguous() and am.device == input_ids.device):
+            # (the tokenizer's dense int64 mask becomes the f32 key mask inside the embedding launch)
+            am = am.to(device=input_ids.device, dtype=torch.float32).contiguous()
         emb = self.embeddings
-        if attention_mask.dtype == torch.int64 and attention_mask.is_contiguous() \
-                and attention_mask.device == input_ids.device:
-            # the tokenizer's int64 mask -> the f32 key mask inside the embedding launch
-            x, am = K.embed_fwd(ids, emb.word_embeddings.weight, emb.position_embeddings.weight, mask=attention_mask)
-        else:
-            am = attention_mask.to(device=input_ids.device, dtype=torch.float32).contiguous()
-            x = K.embed_fwd(ids, emb.word_embeddings.weight, emb.position_embeddings.weight)
-        h, _, _, hT, _ = K.ln_fwd(x, emb.LayerNorm.weight, emb.LayerNorm.bias, 1e-12, out_dtype=torch.float32,
-                                  out_dropout=pdrop, seed_out=seed * 131 + 1, want_stats=False, y2=bf,
-                                  step_ptr=step_ptr)
-        hT = hT if bf else h
-        for li, (lyr, (wqkv, bqkv, wout, w1, w2)) in enumerate(zip(self.transformer.layer, self._weights(dtype))):
-            qkv = K.linear_fwd(hT, wqkv, bqkv)
-            o, _ = K.attn_fwd(qkv, B, T, H, hd, hd ** -0.5, key_mask=am, dropout_p=padrop,
-                              seed=seed * 131 + 7 * li + 2, want_lse=False, step_ptr=step_ptr)
-            sa = K.linear_fwd(o, wout, lyr.attention.out_lin.bias, out_dtype=torch.float32)
-            a, _, _, aT, _ = K.ln_fwd(sa, lyr.sa_layer_norm.weight, lyr.sa_layer_norm.bias, 1e-12,
-                                      out_dtype=torch.float32, res=h, want_stats=False, y2=bf)
-            aT = aT if bf else a
-            f1 = K.linear_fwd(aT, w1, lyr.ffn.lin1.bias, epilogue=K.EPI_GELU)   # frozen tower: no aux
-            f2 = K.linear_fwd(f1, w2, lyr.ffn.lin2.bias, out_dtype=torch.float32)
-            h, _, _, hT, _ = K.ln_fwd(f2, lyr.output_layer_norm.weight, lyr.output_layer_norm.bias, 1e-12,
-                                      out_dtype=torch.float32, res=a, in_dropout=pdrop, seed_in=seed * 131 + 7 * li + 3,
-                                      want_stats=False, y2=bf, step_ptr=step_ptr)
-            hT = hT if bf else h
-        return h.view(B, T, D)
+
+        def layers():
+            # the cached fused weights are (re)built when the first layer is reached
+            for lyr, (wqkv, bqkv, wout, w1, w2) in zip(self.transformer.layer, self._weights(dtype)):
+                yield (wqkv, bqkv, wout, lyr.attention.out_lin.bias, lyr.sa_layer_norm.weight,
+                       lyr.sa_layer_norm.bias, w1, lyr.ffn.lin1.bias, w2, lyr.ffn.lin2.bias,
+                       lyr.output_layer_norm.weight, lyr.output_layer_norm.bias)
+
+        # nothing kept for a backward: no LayerNorm statistics, no lse, plain GELU epilogue
+        h = Fn.text_forward(ids, am, (emb.word_embeddings.weight, emb.position_embeddings.weight,
+                                      emb.LayerNorm.weight, emb.LayerNorm.bias), layers(), B, T, self.dim,
+                            self.n_heads, dtype, self.dropout_p if train else 0.0,
+                            self.attn_dropout_p if train else 0.0, seed, step_ptr, False)[0]
+        return h.view(B, T, self.dim)
 
 
 class TextEncoder(nn.Module):

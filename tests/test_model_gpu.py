@@ -693,6 +693,64 @@ def test_stack_microbatches_match_whole_batch(dev, opts, precision):
     record_parity(f"stack_microbatches_2_vs_1_{precision}", worst_bias_ln_grad_relL2=worst)
 
 
+@pytest.mark.parametrize("precision,D,H,B,n", [("bf16", 128, 2, 16, 8), ("bf16", 128, 2, 128, 5),
+                                               ("fp8", 256, 4, 64, 8), ("fp8", 256, 4, 128, 5)])
+def test_run_stack_microbatches_match_whole_batch_small(dev, opts, precision, D, H, B, n):
+    """modules.run_stack on 2 Blocks (D = 128, H = 2: ViT-B's head_dim 64) with
+    stack_microbatches 2 == 1, at the smallest even-row and odd-sequence shapes
+    at which each of two micro-batches keeps whole 64-row groups (64 rows; 5 x
+    64 rows): the same functions.block_forward / block_backward issued by the
+    micro-batch driver on row slices of whole-batch buffers and by the
+    whole-batch driver. Output, x.grad and every weight gradient bitwise
+    equal; bias / LayerNorm gradients, whose column partials are summed in
+    another grouping, within 1e-5 relative L2 (the bound of
+    test_stack_microbatches_match_whole_batch). Stream-K off as there, for the
+    same reason.
+
+    fp8: the fp8 GEMMs' argument check (M, N >= 256, per launch) rejects D =
+    128 and a micro-batch of 64 rows, so these cases run at D = 256, H = 4 (the
+    smallest width it accepts, head_dim still 64) and the even-row case at
+    (B, n) = (64, 8), the smallest B at n = 8 whose micro-batches (256 rows)
+    it accepts; (128, 5) has 320 rows per micro-batch as it is."""
+    opts(GEMM_SK=0)
+    from tests.helpers import product_config
+    from mae_clip_amd import functions as Fn, modules as Mo
+    bf = torch.bfloat16
+    g = torch.Generator().manual_seed(3)
+    blocks = torch.nn.ModuleList([Mo.Block(D, H) for _ in range(2)])
+    for p in blocks.parameters():    # no parameter at its init value (zero biases, unit LayerNorm weights)
+        p.data.add_(0.05 * torch.randn(p.shape, generator=g))
+    blocks.to(dev)
+    x0 = torch.randn((B, n, D), generator=g).to(dev)
+    gy = torch.randn((B, n, D), generator=g).to(dev)
+    cache = Mo.WeightCache(fp8=precision == "fp8")
+    for blk in blocks:
+        for w in blk.gemm_weights():
+            cache.register(w, w.shape)
+            cache.register_fp8(w)
+    res = {}
+    for S in (1, 2):
+        with product_config(precision=precision, stack_microbatches=S):
+            assert Fn.microbatch_count(Fn.StackSpec(B=B, n=n, D=D, H=H, eps=1e-6, dtype=bf, wT=[])) == S
+            cache.refresh(bf)
+            x = x0.clone().requires_grad_()
+            y = Mo.run_stack(blocks, x, H, bf, cache)
+            y.backward(gy)
+            torch.cuda.synchronize()
+            res[S] = (y.detach(), x.grad, {k: p.grad.clone() for k, p in blocks.named_parameters()})
+            for p in blocks.parameters():
+                p.grad = None
+    (y1, dx1, g1), (y2, dx2, g2) = res[1], res[2]
+    assert torch.isfinite(y1).all() and y1.abs().max() > 0
+    assert torch.equal(y1, y2) and torch.equal(dx1, dx2)
+    for k, a in g1.items():
+        if a.dim() >= 2:
+            assert torch.equal(a, g2[k]), k
+        else:
+            e = ((a - g2[k]).norm() / (a.norm() + 1e-30)).item()
+            assert e < 1e-5, (k, e)
+
+
 @pytest.mark.parametrize("sk", [0, 1])
 def test_captured_step_matches_eager_microbatched(dev, opts, sk):
     """The production combination: C2 model shapes at B = 128, where every

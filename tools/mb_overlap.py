@@ -8,7 +8,7 @@ import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from mae_clip_amd import kernels as K
+from mae_clip_amd import functions as Fn
 
 dev = torch.device("cuda")
 which = sys.argv[1] if len(sys.argv) > 1 else "dec"
@@ -27,16 +27,13 @@ lw = torch.ones(D, device=dev)
 lb = torch.zeros(D, device=dev)
 
 
+spec = Fn.StackSpec(B=B, n=n, D=D, H=H, eps=1e-6, dtype=bf, wT=[(W["qkv"], W["proj"], W["fc1"], W["fc2"])])
+params = [lw, lb, None, bq, None, bp, lw, lb, None, b1, None, b2]   # a Block's stack_params (weights: spec.wT)
+
+
 def block(x, Bs):
-    M = Bs * n
-    h1 = K.ln_fwd(x, lw, lb, 1e-6, out_dtype=bf)[0]
-    qkv = K.linear_fwd(h1, W["qkv"], bias=bq)
-    o, _ = K.attn_fwd(qkv, Bs, n, H, hd, hd ** -0.5)
-    x1 = K.linear_fwd(o, W["proj"], bias=bp, out_dtype=torch.float32, epilogue=K.EPI_RESID, resid=x)
-    h2 = K.ln_fwd(x1, lw, lb, 1e-6, out_dtype=bf)[0]
-    dg = torch.empty((M, 4 * D), device=dev, dtype=bf)
-    a = K.linear_fwd(h2, W["fc1"], bias=b1, epilogue=K.EPI_GELU_D, aux_out=dg)
-    return K.linear_fwd(a, W["fc2"], bias=b2, out_dtype=torch.float32, epilogue=K.EPI_RESID, resid=x1)
+    """the product's forward launch sequence of one block on Bs samples"""
+    return Fn.block_forward(spec, spec.wT[0], params, (None,) * 4, x, Bs)[1]
 
 
 x0 = torch.randn(B * n, D, device=dev, generator=None) * 0.5
