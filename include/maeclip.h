@@ -94,9 +94,17 @@ int32_t maeclip_get_option(int32_t key);
  *           gelu'(aux) (+ resid if resid != NULL)); 4 GELU' (C <- gelu(pre),
  *           aux_out <- gelu'(pre): the backward then needs no transcendental);
  *           5 mul-aux (C <- acc * aux (+ resid if resid != NULL)).
- *           For 1 and 4 aux_out may be NULL (forward-only callers).
+ *           For 1 and 4 aux_out may be NULL (forward-only callers). Any
+ *           other epilogue value is rejected.
  *           aux / aux_out have the operand dtype on the fp32 path, bf16 on the
  *           bf16 path.
+ * batch > 1: A, B and C of batch z start z * strideA / strideB / strideC
+ *   elements after the pointers (a stride of 0 shares the operand). aux,
+ *   aux_out and resid have no stride of their own: batch z reads / writes them
+ *   z * strideC elements after their pointers, rows ldaux / ldr apart, so a
+ *   batched epilogue lays them out like C (ldaux = ldr = ldc). bias is shared
+ *   by the batch; colsum_partial takes maeclip_gemm_colsum_rows(M) rows per
+ *   batch.
  * colsum_partial (optional, f32 [batch*maeclip_gemm_colsum_rows(M)][N]):
  *   per-block column sums of the final C, reduce with maeclip_colsum_reduce.
  * splitk > 1 (epilogue 0, no colsum): K is cut into splitk slices whose fp32

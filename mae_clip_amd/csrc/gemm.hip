@@ -401,6 +401,9 @@ extern "C" int32_t maeclip_gemm(const maeclip_gemm_args* a, void* stream) {
   MC_CHECK_ARG(a->M < (1ll << 31) && a->N < (1ll << 31) && a->K < (1ll << 31), "maeclip_gemm: dims too large");
   MC_CHECK_ARG(a->dtype == MAECLIP_F32 || a->dtype == MAECLIP_BF16, "maeclip_gemm: bad dtype %d", a->dtype);
   MC_CHECK_ARG(a->out_dtype == MAECLIP_F32 || a->out_dtype == MAECLIP_BF16, "maeclip_gemm: bad out dtype");
+  // every path switches on the epilogue with a default: an unknown value would
+  // run another epilogue's kernel (DGELU / MUL_AUX with a null aux)
+  MC_CHECK_ARG(a->epilogue >= EPI_NONE && a->epilogue <= EPI_MUL_AUX, "maeclip_gemm: bad epilogue %d", a->epilogue);
   const int epc = a->dtype == MAECLIP_BF16 ? 8 : 4;
   // 16-B vector loads along the contiguous dimension of each operand
   MC_CHECK_ARG(a->a_layout == LAY_KC ? (a->K % epc == 0 && a->lda % epc == 0)

@@ -1,5 +1,7 @@
-"""Shared test helpers: config switching and product<->oracle model pairs."""
+"""Shared test helpers: config switching, product<->oracle model pairs and the
+fp64 / E32 comparison of the kernel reference tests."""
 import contextlib
+import math
 
 import torch
 
@@ -117,3 +119,49 @@ def train_curve(device, precision="bf16", B=4, steps=5):
             "last_rel": rows[-1]["rel"], "curve": rows,
             "config": "C2 model shapes, train mode (dropout 0 both sides), AdamW lr 1e-3 wd 1e-3 (main.py:54-66, "
                       ":101-103) vs the fp64 CPU oracle + torch.optim.AdamW"}
+
+
+# ------------------------------------------------- kernel reference comparison
+F32, BF16 = torch.float32, torch.bfloat16
+FACTOR = 4.0
+
+
+def f32(x):
+    """the double that equals x rounded to fp32 (what a float argument of the ABI holds)"""
+    return torch.tensor(x, dtype=F32).item()
+
+
+def _bf16_half_ulp(ref, slack):
+    """half the spacing of the bf16 grid at |ref| + slack (8 significand bits):
+    2^(floor(log2 a) - 8), between 2^-9 a and 2^-8 a. The relative form
+    2^-9 |ref| is the value at the top of a binade only; torch's own correctly
+    rounded ref.to(bfloat16) exceeds it for a quarter of random values."""
+    a = ref.abs() + slack
+    _, e = torch.frexp(a)                       # a = m 2^e, m in [0.5, 1): floor(log2 a) = e - 1
+    return torch.where(a > 0, torch.ldexp(torch.ones_like(a), e - 1 - 8), torch.zeros_like(a))
+
+
+def check(name, out, ref64, out32, factor=FACTOR):
+    """kernel max error against the fp64 reference <= factor * E32, E32 = the max
+    error of the fp32 torch result out32; bf16 outputs add the bf16 half-ulp.
+    Returns (kernel error, E32, ratio) for the tables of DESIGN.md section 4."""
+    out = out.detach().cpu()
+    assert out.shape == ref64.shape, (name, out.shape, ref64.shape)
+    e32 = (out32.double() - ref64).abs().max().item()
+    err = (out.double() - ref64).abs()
+    assert torch.isfinite(err).all(), name
+    if out.dtype == BF16:
+        err = (err - _bf16_half_ulp(ref64, factor * e32)).clamp_min(0.0)
+    k = err.max().item()
+    ratio = k / e32 if e32 > 0 else (0.0 if k == 0 else math.inf)
+    print(f"[ratio] {name} {k:.3e} {e32:.3e} {ratio:.3f}")
+    assert k <= factor * e32, f"{name}: kernel error {k:.3e} > {factor} * E32 ({e32:.3e}), ratio {ratio:.2f}"
+    return k, e32, ratio
+
+
+def same_bits(a, b):
+    a, b = a.detach().cpu().contiguous(), b.detach().cpu().contiguous()
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    it = {2: torch.int16, 4: torch.int32}[a.element_size()]
+    return torch.equal(a.view(it), b.view(it))

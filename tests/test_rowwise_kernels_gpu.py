@@ -23,13 +23,13 @@ import torch
 import torch.nn.functional as F
 
 from mae_clip_amd import kernels as K
+from tests.helpers import FACTOR, _bf16_half_ulp, check, f32, same_bits  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F32, BF16 = torch.float32, torch.bfloat16
 LN_D = [4, 60, 256, 260, 512, 768, 1024, 1028, 1280, 1536, 1792, 2048]
 LN_D_ALL_TYPES = (260, 768, 1024)
-FACTOR = 4.0
 
 
 def _gen(seed):
@@ -38,45 +38,6 @@ def _gen(seed):
 
 def _randn(shape, seed, dtype=F32, scale=1.0, shift=0.0):
     return (torch.randn(shape, generator=_gen(seed)) * scale + shift).to(dtype)
-
-
-def f32(x):
-    """the double that equals x rounded to fp32 (what a float argument of the ABI holds)"""
-    return torch.tensor(x, dtype=F32).item()
-
-
-def _bf16_half_ulp(ref, slack):
-    """half the spacing of the bf16 grid at |ref| + slack (8 significand bits):
-    2^(floor(log2 a) - 8), between 2^-9 a and 2^-8 a. The relative form
-    2^-9 |ref| is the value at the top of a binade only; torch's own correctly
-    rounded ref.to(bfloat16) exceeds it for a quarter of random values."""
-    a = ref.abs() + slack
-    _, e = torch.frexp(a)                       # a = m 2^e, m in [0.5, 1): floor(log2 a) = e - 1
-    return torch.where(a > 0, torch.ldexp(torch.ones_like(a), e - 1 - 8), torch.zeros_like(a))
-
-
-def check(name, out, ref64, out32):
-    """kernel max error against the fp64 reference <= FACTOR * E32, E32 = the max
-    error of the fp32 torch result out32; bf16 outputs add the bf16 half-ulp"""
-    out = out.detach().cpu()
-    assert out.shape == ref64.shape, (name, out.shape, ref64.shape)
-    e32 = (out32.double() - ref64).abs().max().item()
-    err = (out.double() - ref64).abs()
-    assert torch.isfinite(err).all(), name
-    if out.dtype == BF16:
-        err = (err - _bf16_half_ulp(ref64, FACTOR * e32)).clamp_min(0.0)
-    k = err.max().item()
-    ratio = k / e32 if e32 > 0 else (0.0 if k == 0 else math.inf)
-    print(f"[ratio] {name} {k:.3e} {e32:.3e} {ratio:.3f}")
-    assert k <= FACTOR * e32, f"{name}: kernel error {k:.3e} > {FACTOR} * E32 ({e32:.3e}), ratio {ratio:.2f}"
-
-
-def same_bits(a, b):
-    a, b = a.detach().cpu().contiguous(), b.detach().cpu().contiguous()
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return False
-    it = {2: torch.int16, 4: torch.int32}[a.element_size()]
-    return torch.equal(a.view(it), b.view(it))
 
 
 def _types(D):
