@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MAECLIP_ABI_VERSION 13
+#define MAECLIP_ABI_VERSION 14
 #ifndef MAECLIP_F32
 #define MAECLIP_F32 0
 #define MAECLIP_BF16 1
@@ -628,7 +628,15 @@ int32_t maeclip_mae_loss_bwd_partial_rows(int32_t B, int32_t L);
  * dI, dT optional: d loss / d I, T for the rows [grad_row0, grad_row0 +
  * grad_rows) only (grad_rows 0 = to the end), stored from row 0 of dI / dT --
  * under data parallelism each rank asks for its own slice of the gathered batch.
- * workspace: >= maeclip_clip_loss_workspace(N, P, number of gradient rows). */
+ * workspace: >= maeclip_clip_loss_workspace(N, P, number of gradient rows).
+ * Learnable temperature (ABI 14), both optional (NULL: the by-value field, bit
+ * for bit). log_temperature: device f32 theta = ln tau; every kernel of the call
+ * then uses tau = expf(*log_temperature) and ignores `temperature`, so a
+ * captured graph follows the value in device memory. d_log_temperature: device
+ * f32 output, d loss / d theta = sum_ij (dS_ij S_ij - dL_ij L_ij) over the rows
+ * i in [grad_row0, grad_row0 + grad_rows) (the slices of disjoint row ranges
+ * add up to the whole derivative); needs log_temperature, dI and dT. One more
+ * launch (a one-workgroup fixed-order sum), deterministic like the rest. */
 typedef struct {
   const float* I;
   const float* T;
@@ -643,6 +651,8 @@ typedef struct {
   int64_t grad_row0, grad_rows;
   void* workspace;
   size_t ws_bytes;
+  const float* log_temperature;
+  float* d_log_temperature;
 } maeclip_clip_args;
 size_t maeclip_clip_loss_workspace(int64_t N, int64_t P, int64_t grad_rows);
 int32_t maeclip_clip_loss(const maeclip_clip_args* args, void* stream);

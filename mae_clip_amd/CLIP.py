@@ -17,6 +17,8 @@ all-reduce of parameter gradients yields the exact global-batch gradient.
 """
 from __future__ import annotations
 
+import math
+
 import torch
 from torch import nn
 import torch.nn.functional as F
@@ -42,6 +44,14 @@ class CLIPModel(nn.Module):
         self.image_projection = ProjectionHead(embedding_dim=image_embedding)
         self.text_projection = ProjectionHead(embedding_dim=text_embedding)
         self.temperature = temperature
+        # config.learnable_temperature: theta = ln tau as a trained fp32 parameter on
+        # the device (tau = exp(theta) > 0); the loss kernels read it there, so a
+        # captured step follows it. self.temperature stays the constructor's value.
+        # No clamp of theta yet.
+        if CFG.learnable_temperature:
+            self.log_temperature = nn.Parameter(torch.tensor([math.log(temperature)], dtype=torch.float32))
+        else:
+            self.log_temperature = None
         self.mask_ratio = CFG.mask_ratio
         self.mae_weight = CFG.mae_weight
         self.norm_pix_loss = CFG.norm_pix_loss
@@ -79,6 +89,14 @@ class CLIPModel(nn.Module):
                 self.text_encoder.model.register_weights(c)
             self._cache = c
         return self._cache
+
+    def current_temperature(self) -> float:
+        """tau as the loss uses it now: exp(log_temperature) when the temperature
+        is learnable, else the constructor's float. Reads the parameter back from
+        the device, so it synchronises with the stream: not for the step loop."""
+        if self.log_temperature is None:
+            return float(self.temperature)
+        return float(torch.exp(self.log_temperature.detach().float()).item())
 
     def _world(self):
         pg = self.process_group
@@ -151,7 +169,7 @@ class CLIPModel(nn.Module):
         image_embeddings = self.image_projection(feat, seed=seed + 29, step_ptr=sc, bwd_step_ptr=snap)
         text_embeddings = self.text_projection(text_features, seed=seed + 31, step_ptr=sc, bwd_step_ptr=snap)
         clip = clip_loss(image_embeddings, text_embeddings, self.temperature,
-                         group=self.process_group if world > 1 else None)
+                         group=self.process_group if world > 1 else None, log_temperature=self.log_temperature)
         loss = clip
         self.last_losses = {"clip": clip.detach()}
         if mae:
@@ -186,15 +204,23 @@ class CLIPModel(nn.Module):
         return loss
 
 
-def clip_loss(image_embeddings, text_embeddings, temperature=1.0, group=None):
-    """CLIP.py:34-43 on the fused fp32 kernel (group: data-parallel gather)."""
-    if torch.is_grad_enabled() and (image_embeddings.requires_grad or text_embeddings.requires_grad):
-        return Fn.ClipLossFn.apply(image_embeddings, text_embeddings, temperature, group)
+def clip_loss(image_embeddings, text_embeddings, temperature=1.0, group=None, log_temperature=None):
+    """CLIP.py:34-43 on the fused fp32 kernel (group: data-parallel gather).
+    log_temperature (f32 [1] device tensor, theta = ln tau): the kernel takes
+    tau = exp(theta) from it, with or without autograd, and `temperature` is
+    not used."""
+    lt = log_temperature
+    if torch.is_grad_enabled() and (image_embeddings.requires_grad or text_embeddings.requires_grad
+                                    or (lt is not None and lt.requires_grad)):
+        if lt is None:
+            return Fn.ClipLossFn.apply(image_embeddings, text_embeddings, temperature, group)
+        return Fn.ClipLossFn.apply(image_embeddings, text_embeddings, temperature, group, lt)
     I, T = image_embeddings.contiguous(), text_embeddings.contiguous()
     if group is not None:
         from .distributed import all_gather_rows
         I, T = all_gather_rows(I, group), all_gather_rows(T, group)
-    loss, _, _ = K.clip_loss(I, T, temperature, want_grad=False)
+    loss, _, _ = K.clip_loss(I, T, temperature, want_grad=False,
+                             log_temperature=None if lt is None else lt.detach())
     return loss
 
 

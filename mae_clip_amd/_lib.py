@@ -16,7 +16,7 @@ F32, BF16 = 0, 1
 # plan options (include/maeclip.h MAECLIP_OPT_*), by name without the prefix
 OPTIONS = ("GEMM_BM", "GEMM_SK", "GEMM_SPLIT", "GEMM_SPLIT_D", "GEMM_SPLIT_MINK", "GEMM_BM128", "GEMM_GRID",
            "WG_SK", "ATTN_TWO", "ATTN_ROWS", "ATTN_DIAG", "ATTN_BW16", "ATTN_FW16")
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 c_i32, c_i64, c_f32, c_u64, c_vp, c_sz = C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_void_p, C.c_size_t
 
@@ -117,7 +117,7 @@ class ClipArgs(C.Structure):
     _fields_ = [("I", c_vp), ("T", c_vp), ("ld_I", c_i64), ("ld_T", c_i64), ("N", c_i64), ("P", c_i64),
                 ("temperature", c_f32), ("loss", c_vp), ("row_loss_out", c_vp), ("dI", c_vp), ("dT", c_vp),
                 ("ld_dI", c_i64), ("ld_dT", c_i64), ("grad_row0", c_i64), ("grad_rows", c_i64),
-                ("workspace", c_vp), ("ws_bytes", c_sz)]
+                ("workspace", c_vp), ("ws_bytes", c_sz), ("log_temperature", c_vp), ("d_log_temperature", c_vp)]
 
 
 class WgradProblem(C.Structure):

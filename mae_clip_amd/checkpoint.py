@@ -13,6 +13,12 @@ lacks the mae_decoder.* keys: load_checkpoint(strict="reference") accepts
 exactly that case, keeps the decoder's own initialisation and reports the keys
 it did not find (missing_out).
 
+With config.learnable_temperature the state_dict has one more key,
+`log_temperature` (fp32 [1]), which travels with it like every other weight.
+The reference has no such key: a checkpoint saved with the flag off (or a
+reference best.pt) does not load strictly into a model built with the flag on,
+and the other way round -- load it with strict=False and set the parameter.
+
 For resuming a run this module adds what the bare state_dict cannot carry:
   * the optimizer state (AdamW exp_avg / exp_avg_sq / step, torch.optim format),
   * the model's training step, which keys the MAE mask noise and every dropout

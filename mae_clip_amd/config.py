@@ -31,6 +31,8 @@ max_length = 200
 pretrained = False  # reference: True (hub download); no network here
 trainable = True
 temperature = 1.0
+learnable_temperature = False   # True: CLIPModel trains log_temperature = ln(temperature) (one fp32 parameter,
+                                # read by the loss kernels on the device); put it in a weight_decay = 0 group
 
 # image size
 size = 224

@@ -32,6 +32,11 @@
 //             rows [grad_row0, +grad_rows): data parallel, the local slice).
 //             Workgroup (0, 0) writes loss = sum_i rl_i (and the per-row rl).
 // No partial-gradient slabs and no reduction launch.
+// Learnable temperature (theta = ln tau on the device, tau = exp(theta)): with
+//   L = A / tau, S = B tau:  d loss / d theta = sum_ij (dS_ij S_ij - dL_ij L_ij),
+// dS_ij the row-i term Y_ij (G_ij - rl_i), not the symmetrised Dm. The grad
+// launch sums it per gradient row (column block 0 only) and a fourth, one-
+// workgroup launch adds the rows -- only when d_log_temperature is asked for.
 // Products workgroup = 4 waves; wave w computes one of the four 16x16 dot tiles
 // of a j-tile (S1 = I_j.I_i, S2 = T_j.T_i, L = I_j.T_i, L^T = T_j.I_i), laid
 // out transposed (row = j on the accumulator registers, column = i on the lane)
@@ -61,9 +66,20 @@ struct ClipK {
   float* Lm;           // [N][NP] L = T I^T / tau
   float* Ltm;          // [N][NP] L^T
   int g0, Ng;          // gradient rows
+  const float* ltau;   // device theta = ln tau (learnable temperature), or null: tau by value
+  float* dtrow;        // [16 * gradient row blocks]: per-row terms of d loss / d theta
 };
 
 __device__ __forceinline__ v4f mma4(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+// tau of the call: the by-value field, or exp(theta) of the device theta. The one
+// expression every kernel takes it from, so that the stored matrices and the
+// gradient use the same value bit for bit (exp(0) = 1 exactly: theta = 0 is the
+// by-value tau = 1). Wave-uniform, and back in a scalar register after the exp.
+__device__ __forceinline__ float clip_tau(const ClipK& a) {
+  if (!a.ltau) return a.tau;
+  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(expf(*a.ltau))));
+}
 
 __device__ __forceinline__ void merge_ms(float& m, float& s, float m2, float s2) {
   const float M = fmaxf(m, m2);
@@ -161,7 +177,7 @@ __global__ void __launch_bounds__(NT) clip_products_kernel(const ClipK a) {
   const int js = blockIdx.y;
   const int jt0 = js * a.nrep, njt = (a.N + 15) / 16;
   const int jt1 = min(jt0 + a.nrep, njt);
-  const float tau = a.tau, itau = 1.f / tau;
+  const float tau = clip_tau(a), itau = 1.f / tau;
   const int N = a.N;
 
   v4f ir[4 * NB];
@@ -303,14 +319,22 @@ __global__ void __launch_bounds__(NT) clip_stats_kernel(const ClipK a) {
 
 // ------------------------------------------------------------------ grad
 // grid (gradient 16-row blocks, P / 16), or (1, 1) for the loss alone.
+// DT (learnable temperature): the workgroups of column block 0 also sum, per
+// gradient row i, t_i = sum_j (dS_ij S_ij - dL_ij L_ij) with dS_ij = Y_ij (G_ij -
+// rl_i) (d loss / d theta = sum_i t_i at tau = exp(theta): dS/dtheta = S,
+// dL/dtheta = -L) from the values the tile loop has in registers: per lane over
+// its j, then the four 4-j groups of a row, then the waves in wave order ->
+// dtrow (0 for the rows of the block outside the slice or past N).
+template <bool DT>
 __global__ void __launch_bounds__(NT) clip_grad_kernel(const ClipK a, float* loss, float* row_loss, float* dI,
                                                        int64_t lddI, float* dT, int64_t lddT) {
   __shared__ __attribute__((aligned(16))) v4f accs[2][4][64];
   __shared__ float red[NT / 64];
+  __shared__ float dts[DT ? NT / 64 : 1][16];
   const int lane = threadIdx.x & 63, g = lane >> 4, il = lane & 15;
   const int w = threadIdx.x >> 6;
   const int N = a.N;
-  const float tau = a.tau, itau = 1.f / tau, inv2n = 0.5f / (float)N;
+  const float tau = clip_tau(a), itau = 1.f / tau, inv2n = 0.5f / (float)N;
   const float* st = a.stat;   // [8][N]: mS, zS, mR, zR, mC, zC, c, rl
   const float* rlv = a.stat + 7LL * N;
   if (blockIdx.x == 0 && blockIdx.y == 0) {
@@ -334,6 +358,8 @@ __global__ void __launch_bounds__(NT) clip_grad_kernel(const ClipK a, float* los
   const float ci = si[6], rli = si[7];
   const int64_t rowo = (int64_t)irow * a.NP;
   v4f accI = {0.f, 0.f, 0.f, 0.f}, accT = {0.f, 0.f, 0.f, 0.f};
+  const bool dtb = DT && blockIdx.y == 0;   // workgroup-uniform
+  float dth = 0.f;
   const int njt = (N + 15) / 16;
   // two j-tiles per step, every load of both issued before any is used
   for (int jt0 = w; jt0 < njt; jt0 += 8) {
@@ -379,13 +405,26 @@ __global__ void __launch_bounds__(NT) clip_grad_kernel(const ClipK a, float* los
           accI = mma4(xt[h][r], bLt, accI);
           accT = mma4(xt[h][r], bD, accT);
           accT = mma4(xi[h][r], bL, accT);
+          if (DT && dtb && ok) dth += Yij * (Gij - rli) * S - dLij * Lij;
         }
       }
     }
   }
   accs[0][w][lane] = accI;
   accs[1][w][lane] = accT;
+  if (DT && dtb) {
+    dth += __shfl_xor(dth, 16, 64);
+    dth += __shfl_xor(dth, 32, 64);
+    if (g == 0) dts[w][il] = dth;
+  }
   __syncthreads();
+  if (DT && dtb && threadIdx.x < 16) {
+    // irow repeats row N - 1 past the end, and the last block of a slice runs
+    // past it: those rows are no part of the sum
+    const int i = i0 + il;
+    const float t = (dts[0][il] + dts[1][il]) + (dts[2][il] + dts[3][il]);
+    a.dtrow[16 * (int)blockIdx.x + il] = (i < N && i < a.g0 + a.Ng) ? t : 0.f;
+  }
   if (w < 2) {
     // lane holds dI^T[p = pc + 4g + r][i = il] -> row i, 4 consecutive p
     const v4f s = (accs[w][0][lane] + accs[w][1][lane]) + (accs[w][2][lane] + accs[w][3][lane]);
@@ -396,6 +435,21 @@ __global__ void __launch_bounds__(NT) clip_grad_kernel(const ClipK a, float* los
       *(v4f*)(dst + pc + 4 * g) = s;
     }
   }
+}
+
+// d loss / d theta = the sum of the n per-row terms: one workgroup, in double and
+// in a fixed order (strided per-lane sums, then a binary tree through LDS)
+__global__ void __launch_bounds__(NT) clip_dtemp_kernel(const float* __restrict__ rows, int n, float* __restrict__ out) {
+  __shared__ double red[NT];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += NT) s += (double)rows[i];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = NT / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = (float)red[0];
 }
 
 // ------------------------------------------------------------ geometry
@@ -413,10 +467,13 @@ void products_geometry(int64_t N, int& nrep, int& Js) {
 
 size_t off_matrices(int64_t N, int Js) { return ((size_t)Js * 3 * N * 2 + 8 * (size_t)N + 3) / 4 * 4; }
 
+// part1, stat, the three matrices, then the per-row terms of d loss / d theta
+// (at most stride16(N): the 16-row blocks of a slice of g rows from row r0 are
+// ceil(g / 16) <= ceil(N / 16))
 size_t ws_floats(int64_t N) {
   int nrep, Js;
   products_geometry(N, nrep, Js);
-  return off_matrices(N, Js) + 3 * (size_t)N * stride16(N);
+  return off_matrices(N, Js) + 3 * (size_t)N * stride16(N) + (size_t)stride16(N);
 }
 
 template <int NB>
@@ -442,6 +499,8 @@ int run(const maeclip_clip_args& a, hipStream_t s) {
   k.Ltm = k.Lm + (size_t)N * k.NP;
   k.g0 = grad ? (int)a.grad_row0 : 0;
   k.Ng = (int)Ng;
+  k.ltau = a.log_temperature;
+  k.dtrow = k.Ltm + (size_t)N * k.NP;
   const unsigned nb = (unsigned)((N + 15) / 16);
   hipLaunchKernelGGL((clip_products_kernel<NB>), dim3(nb, k.Js), dim3(NT), 0, s, k);
   MC_CHECK_LAUNCH("maeclip_clip_loss(products)");
@@ -449,8 +508,16 @@ int run(const maeclip_clip_args& a, hipStream_t s) {
   MC_CHECK_LAUNCH("maeclip_clip_loss(stats)");
   const bool g = grad && Ng > 0;
   const int64_t lddI = a.ld_dI ? a.ld_dI : a.P, lddT = a.ld_dT ? a.ld_dT : a.P;
-  hipLaunchKernelGGL(clip_grad_kernel, dim3(g ? (unsigned)((Ng + 15) / 16) : 1u, g ? (unsigned)(a.P / 16) : 1u),
-                     dim3(NT), 0, s, k, a.loss, a.row_loss_out, g ? a.dI : nullptr, lddI, a.dT, lddT);
+  const dim3 ggrid(g ? (unsigned)((Ng + 15) / 16) : 1u, g ? (unsigned)(a.P / 16) : 1u);
+  if (a.d_log_temperature) {   // validated: grad holds, so Ng >= 1
+    hipLaunchKernelGGL(clip_grad_kernel<true>, ggrid, dim3(NT), 0, s, k, a.loss, a.row_loss_out, a.dI, lddI, a.dT, lddT);
+    MC_CHECK_LAUNCH("maeclip_clip_loss(grad)");
+    hipLaunchKernelGGL(clip_dtemp_kernel, dim3(1), dim3(NT), 0, s, k.dtrow, 16 * (int)ggrid.x, a.d_log_temperature);
+    MC_CHECK_LAUNCH("maeclip_clip_loss(dtemp)");
+    return 0;
+  }
+  hipLaunchKernelGGL(clip_grad_kernel<false>, ggrid, dim3(NT), 0, s, k, a.loss, a.row_loss_out, g ? a.dI : nullptr, lddI,
+                     a.dT, lddT);
   MC_CHECK_LAUNCH("maeclip_clip_loss(grad)");
   return 0;
 }
@@ -468,7 +535,11 @@ extern "C" int32_t maeclip_clip_loss(const maeclip_clip_args* a, void* stream) {
   MC_CHECK_ARG(a->N > 0 && a->N <= 16384, "maeclip_clip_loss: N must be in [1, 16384] (got %lld)", (long long)a->N);
   MC_CHECK_ARG(a->P == 64 || a->P == 128 || a->P == 256 || a->P == 512,
                "maeclip_clip_loss: P must be 64, 128, 256 or 512 (got %lld)", (long long)a->P);
-  MC_CHECK_ARG(a->temperature > 0.f, "maeclip_clip_loss: temperature must be > 0");
+  MC_CHECK_ARG(a->log_temperature || a->temperature > 0.f, "maeclip_clip_loss: temperature must be > 0");
+  MC_CHECK_ARG(((uintptr_t)a->log_temperature & 3) == 0 && ((uintptr_t)a->d_log_temperature & 3) == 0,
+               "maeclip_clip_loss: log_temperature / d_log_temperature must be 4-byte aligned");
+  MC_CHECK_ARG(!a->d_log_temperature || (a->log_temperature && a->dI && a->dT),
+               "maeclip_clip_loss: d_log_temperature needs log_temperature, dI and dT");
   const int64_t ldi = a->ld_I ? a->ld_I : a->P, ldt = a->ld_T ? a->ld_T : a->P;
   MC_CHECK_ARG(ldi >= a->P && ldt >= a->P && ldi % 4 == 0 && ldt % 4 == 0 && ((uintptr_t)a->I & 15) == 0 &&
                    ((uintptr_t)a->T & 15) == 0,

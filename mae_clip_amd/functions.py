@@ -1005,7 +1005,12 @@ class ClipLossFn(torch.autograd.Function):
     the parameter gradients is the exact global-batch gradient."""
 
     @staticmethod
-    def forward(ctx, I, T, temperature, group=None):
+    def forward(ctx, I, T, temperature, group=None, log_temperature=None):
+        """log_temperature (CLIPModel.log_temperature, f32 [1]): the kernel reads
+        tau = exp(theta) from its device memory instead of the float; when it
+        requires grad, d loss / d theta comes out of the same call. Under data
+        parallelism it is the sum over the rank's own rows, so the SUM
+        all-reduce of the parameter gradients needs no rescale."""
         I = I.contiguous()
         T = T.contiguous()
         rows = None
@@ -1018,17 +1023,34 @@ class ClipLossFn(torch.autograd.Function):
                 I = all_gather_rows(I, group)
                 T = all_gather_rows(T, group)
                 rows = (rank * B, B)
-        loss, dI, dT = K.clip_loss(I, T, temperature, want_grad=True, grad_rows=rows)
-        ctx.grads = (dI, dT)
+        lt = None if log_temperature is None else log_temperature.detach()
+        ctx.theta = log_temperature if lt is not None and ctx.needs_input_grad[4] else None
+        if ctx.theta is not None:
+            loss, dI, dT, dth = K.clip_loss(I, T, temperature, want_grad=True, grad_rows=rows, log_temperature=lt,
+                                            want_dtemp=True)
+            ctx.grads = (dI, dT, dth)
+        else:
+            loss, dI, dT = K.clip_loss(I, T, temperature, want_grad=True, grad_rows=rows, log_temperature=lt)
+            ctx.grads = (dI, dT)
+        ctx.arena = _arena()
         return loss
 
     @staticmethod
     def backward(ctx, gl):
-        dI, dT = ctx.grads
+        grads = ctx.grads
         ctx.grads = None
-        # scaled in place by the device grad_output: one launch, no host sync
-        K.scale_by_scalar(gl.reshape(1).contiguous(), 1.0, dI, dT, dI, dT)
-        return dI, dT, None, None
+        s = gl.reshape(1).contiguous()
+        if ctx.theta is None:
+            dI, dT = grads
+            # scaled in place by the device grad_output: one launch, no host sync
+            K.scale_by_scalar(s, 1.0, dI, dT, dI, dT)
+            return dI, dT, None, None, None
+        # dI, dT are the halves of one buffer: scaled in place as one tensor, and
+        # d theta into the parameter's gradient slot, in the same launch
+        dI, dT, dth = grads
+        both = dI._base.view(-1)
+        _, dth = K.scale_by_scalar(s, 1.0, both, dth, both, gout(ctx.arena, ctx.theta))
+        return dI, dT, None, None, dth
 
 
 class CombineLossFn(torch.autograd.Function):

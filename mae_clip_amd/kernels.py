@@ -764,29 +764,45 @@ def mae_loss_bwd(pred, img, mask, p, norm_pix, grad_out, mask_count, loss_scale=
 
 
 # --------------------------------------------------------------- CLIP loss
-def clip_loss(I, T, temperature, want_grad=True, grad_rows=None, row_loss=False):
+def clip_loss(I, T, temperature, want_grad=True, grad_rows=None, row_loss=False, log_temperature=None,
+              want_dtemp=False):
     """Fused soft-target CLIP loss (CLIP.py:34-43). grad_rows = (row0, count):
     gradients only for that slice of the rows (data parallel: the local rows
-    of the gathered batch); default all rows. Returns (loss, dI, dT[, rl])."""
+    of the gathered batch); default all rows. Returns (loss, dI, dT[, rl]).
+
+    log_temperature (device f32 [1], theta = ln tau): the kernels read tau =
+    exp(theta) from device memory and ignore `temperature`. want_dtemp (needs
+    log_temperature and want_grad): d loss / d theta of the gradient rows as a
+    device f32 [1] tensor, appended to the result; dI and dT are then the two
+    halves of one buffer (dI._base), so one launch can scale both."""
     _dev(I, T)
     N, P = I.shape
     r0, nr = (0, N) if grad_rows is None else grad_rows
     if not (0 <= r0 and nr >= 1 and r0 + nr <= N):
         raise ValueError(f"clip_loss: gradient rows {grad_rows} out of range for N={N}")
+    if log_temperature is not None:
+        _dev(log_temperature)
+        if log_temperature.dtype != torch.float32 or log_temperature.numel() != 1:
+            raise ValueError("clip_loss: log_temperature must be one f32 element")
+    if want_dtemp and (log_temperature is None or not want_grad):
+        raise ValueError("clip_loss: want_dtemp needs log_temperature and want_grad")
     ws_bytes = int(L.lib().maeclip_clip_loss_workspace(N, P, nr if want_grad else 0))
     ws = torch.empty((ws_bytes // 4,), device=I.device, dtype=torch.float32)
     loss = torch.empty((), device=I.device, dtype=torch.float32)
-    dI = torch.empty((nr, P), device=I.device, dtype=torch.float32) if want_grad else None
-    dT = torch.empty((nr, P), device=I.device, dtype=torch.float32) if want_grad else None
+    if want_dtemp:
+        dI, dT = torch.empty((2, nr, P), device=I.device, dtype=torch.float32).unbind(0)
+    else:
+        dI = torch.empty((nr, P), device=I.device, dtype=torch.float32) if want_grad else None
+        dT = torch.empty((nr, P), device=I.device, dtype=torch.float32) if want_grad else None
     rl = torch.empty((N,), device=I.device, dtype=torch.float32) if row_loss else None
+    dth = torch.empty((1,), device=I.device, dtype=torch.float32) if want_dtemp else None
     a = L.ClipArgs(I=I.data_ptr(), T=T.data_ptr(), ld_I=I.stride(0), ld_T=T.stride(0), N=N, P=P,
                    temperature=float(temperature), loss=loss.data_ptr(), row_loss_out=_ptr(rl), dI=_ptr(dI),
                    dT=_ptr(dT), ld_dI=P, ld_dT=P, grad_row0=r0, grad_rows=nr, workspace=ws.data_ptr(),
-                   ws_bytes=ws_bytes)
+                   ws_bytes=ws_bytes, log_temperature=_ptr(log_temperature), d_log_temperature=_ptr(dth))
     _call("maeclip_clip_loss", C.byref(a), _stream())
-    if row_loss:
-        return loss, dI, dT, rl
-    return loss, dI, dT
+    out = (loss, dI, dT) + ((rl,) if row_loss else ()) + ((dth,) if want_dtemp else ())
+    return out
 
 
 # ------------------------------------------------------------ multi-tensor
