@@ -58,7 +58,10 @@ int32_t maeclip_device_count(void);
  *   ATTN_ROWS        1: fp32 attention on the streaming rows path
  *   ATTN_DIAG        diagonal backward (hd 32 on, hd 64 at npad >= 192); 0 / 1
  *   ATTN_BW16        16-wave backward beyond MAXW tiles (default hd 32); 0 / 1
- *   ATTN_FW16        16-wave forward when LDS leaves one workgroup (default 1) */
+ *   ATTN_FW16        16-wave forward when LDS leaves one workgroup (default 1)
+ *   ATTN_STREAM      bf16 streamed attention kernels (LDS footprint independent
+ *                    of n): -1 where the resident images do not fit, 1 at
+ *                    every n, 0 never (such shapes are rejected) */
 enum {
   MAECLIP_OPT_GEMM_BM = 0,
   MAECLIP_OPT_GEMM_SK = 1,
@@ -73,7 +76,8 @@ enum {
   MAECLIP_OPT_ATTN_DIAG = 10,
   MAECLIP_OPT_ATTN_BW16 = 11,
   MAECLIP_OPT_ATTN_FW16 = 12,
-  MAECLIP_OPT_COUNT = 13
+  MAECLIP_OPT_ATTN_STREAM = 13,
+  MAECLIP_OPT_COUNT = 14
 };
 /* returns the previous value, or INT32_MIN for an unknown key */
 int32_t maeclip_set_option(int32_t key, int32_t value);
@@ -251,6 +255,14 @@ int32_t maeclip_wgrad_grouped(const maeclip_wgrad_problem* probs, int32_t nprob,
  * the fp32 streamed "rows" path takes the mask (no dropout) and everything
  * else is rejected. fp32 forward / backward at any n: past the LDS images
  * (n ~ 540 at hd 32) 64-row blocks are streamed (no dropout there).
+ * bf16 at any n: the resident kernels hold a head's whole K / V (backward:
+ * Q / dO too) in LDS, up to n = 576 at hd 64 and n = 1216 (forward) / 1152
+ * (backward) at hd 32; past that the streamed kernels take the call (option
+ * ATTN_STREAM; forward and backward decide independently, lse and o are the
+ * same convention): 64-row blocks through a two-slot LDS ring, the backward
+ * as a dQ and a dK / dV launch plus a column-sum launch for colsum_partial,
+ * deterministic, nothing allocated. They take neither key_mask nor dropout
+ * (rejected with -1 before any launch), and q8 by the standalone pass.
  * bwd: dout [B*n, ld_o], dqkv [B*n, ld_dqkv]; colsum_partial optional
  * [B, 3*H*hd] per-sample column sums of dqkv (qkv bias gradient). */
 typedef struct {
@@ -273,7 +285,7 @@ typedef struct {
    * the backward, whose row length must be a multiple of 128): the bytes of
    * maeclip_quant_blocks_fp8 of the bf16 output as stored. Written by the
    * bf16 MFMA kernels' own stores; the other variants (fp32, the diagonal and
-   * row-streaming backward) run the standalone pass after the kernel. */
+   * row-streaming backward, the bf16 streamed kernels) run the standalone pass after the kernel. */
   void* q8;
   int64_t ldq8;
   uint8_t* q8_scale;

@@ -23,7 +23,8 @@ void set_error(const char* fmt, ...) {
 namespace {
 const char* const g_opt_names[MAECLIP_OPT_COUNT] = {
     "GEMM_BM",   "GEMM_SK",   "GEMM_SPLIT", "GEMM_SPLIT_D", "GEMM_SPLIT_MINK", "GEMM_BM128", "GEMM_GRID",
-    "WG_SK",     "ATTN_TWO",  "ATTN_ROWS",  "ATTN_DIAG",    "ATTN_BW16",       "ATTN_FW16"};
+    "WG_SK",     "ATTN_TWO",  "ATTN_ROWS",  "ATTN_DIAG",    "ATTN_BW16",       "ATTN_FW16",
+    "ATTN_STREAM"};
 std::atomic<int32_t> g_opt[MAECLIP_OPT_COUNT];
 std::once_flag g_opt_once;
 void opt_init() {

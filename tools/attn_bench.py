@@ -1,6 +1,9 @@
 """Attention fwd/bwd kernel time at the production shapes of the C2 step
 (ViT-B/16 MAE+CLIP, B=256) vs torch SDPA (for reference only), plus a
-numerics check of the bwd against fp32 torch autograd on a small batch."""
+numerics check of the bwd against fp32 torch autograd on a small batch.
+Rows with a sixth entry run under that ATTN_STREAM value: the streamed kernels
+(the default past the LDS-resident limit) next to the resident ones at shapes
+both take."""
 import json
 import os
 import sys
@@ -12,7 +15,10 @@ from mae_clip_amd import kernels as K
 
 dev = torch.device("cuda")
 SHAPES = [("enc", 256, 50, 12, 64), ("dec", 256, 197, 16, 32), ("text", 256, 25, 12, 64),
-          ("C1 enc", 256, 197, 12, 64), ("C4 enc", 128, 145, 16, 64), ("C4 dec", 128, 577, 16, 32)]
+          ("C1 enc", 256, 197, 12, 64), ("C4 enc", 128, 145, 16, 64), ("C4 dec", 128, 577, 16, 32),
+          ("C4 dec streamed", 128, 577, 16, 32, 1), ("L/14@336 n=576", 128, 576, 16, 64),
+          ("L/14@336 n=576 streamed", 128, 576, 16, 64, 1), ("L/14@336 unmasked", 128, 577, 16, 64),
+          ("L/14@448", 32, 1025, 16, 64)]
 
 
 def time_fn(fn, reps=20):
@@ -33,7 +39,8 @@ def ref(qkv, B, n, H, hd):
     return F.scaled_dot_product_attention(x[0], x[1], x[2]).permute(0, 2, 1, 3).reshape(B * n, H * hd)
 
 
-for name, B, n, H, hd in SHAPES:
+for name, B, n, H, hd, *opt in SHAPES:
+    K.set_option("ATTN_STREAM", opt[0] if opt else None)
     D = H * hd
     qkv = (torch.randn(B * n, 3 * D, device=dev)).to(torch.bfloat16)
     dout = (torch.randn(B * n, D, device=dev) * 0.1).to(torch.bfloat16)
