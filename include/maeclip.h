@@ -557,6 +557,35 @@ int32_t maeclip_l2_normalize(const float* x, float* y, int64_t M, int64_t P, int
 int32_t maeclip_topk_rows(const float* s, int64_t Q, int64_t N, int64_t lds, int32_t k, float* vals, int64_t* idx,
                           void* stream);
 
+/* Retrieval evaluation: similarity and top-k in one streamed pass, the [Q][N]
+ * similarity matrix never written. maeclip_sim_topk: q fp32 [Q][P] (row stride
+ * ldq), g fp32 [N][P] (row stride ldg), used as given (normalise first with
+ * maeclip_l2_normalize; inputs are assumed finite). For every query row the k
+ * largest s_ij = sum_p q_ip g_jp over j < N: vals fp32 [Q][k] descending, idx
+ * int64 [Q][k], ties broken by the lower index (the order of
+ * maeclip_topk_rows). The products are exact f32 fma chains in a fixed order,
+ * so the result is deterministic and does not depend on the split count.
+ * Limits: 1 <= k <= min(N, 64); P % 16 == 0, 16 <= P <= 512; Q >= 0 (0 is a
+ * no-op); 1 <= N < 2^31 - 256; ldq, ldg >= P. Larger k: maeclip_gemm +
+ * maeclip_topk_rows.
+ * splits: over how many workgroups per 64-row query block the gallery is
+ * divided (0 = automatic: enough to fill the chip when Q is small; > 0 =
+ * forced, clamped to the number of 16-row gallery tiles). With more than one
+ * split the partial lists go through ws (maeclip_sim_topk_workspace bytes,
+ * 8-byte aligned) and a second launch merges them.
+ * q_label int64 [Q] and g_label int64 [N], both or neither, with first_hit
+ * int32 [Q]: first_hit[q] = the smallest t < k with g_label[idx[q][t]] ==
+ * q_label[q], or k when there is none (recall@K = mean(first_hit < K) for any
+ * K <= k).
+ * maeclip_sim_topk_splits (host only): the split count a launch will use, < 0
+ * on bad arguments. maeclip_sim_topk_workspace (host only): bytes of ws, 0
+ * with one split. No allocation, no synchronisation, no atomics. */
+int32_t maeclip_sim_topk_splits(int64_t Q, int64_t N, int64_t P, int32_t k, int32_t splits);
+int64_t maeclip_sim_topk_workspace(int64_t Q, int64_t N, int64_t P, int32_t k, int32_t splits);
+int32_t maeclip_sim_topk(const float* q, const float* g, int64_t Q, int64_t N, int64_t P, int64_t ldq, int64_t ldg,
+                         int32_t k, int32_t splits, float* vals, int64_t* idx, const int64_t* q_label,
+                         const int64_t* g_label, int32_t* first_hit, void* ws, int64_t ws_bytes, void* stream);
+
 /* timm _pos_embed on the visible tokens: x[b,0] = cls + pos[0];
  * x[b,1+j] = y[b*keep+j] + pos[1+ids_shuffle[b,j]]; bwd: dy rows, dpos, dcls. */
 typedef struct {

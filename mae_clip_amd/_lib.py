@@ -170,6 +170,10 @@ _SIGS = {
     "maeclip_image_preprocess_u8": (c_i32, [C.POINTER(PreprocessArgs), c_vp]),
     "maeclip_l2_normalize": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_f32, c_vp]),
     "maeclip_topk_rows": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "maeclip_sim_topk_splits": (c_i32, [c_i64, c_i64, c_i64, c_i32, c_i32]),
+    "maeclip_sim_topk_workspace": (c_i64, [c_i64, c_i64, c_i64, c_i32, c_i32]),
+    "maeclip_sim_topk": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp,
+                                 c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "maeclip_attn_fwd": (c_i32, [C.POINTER(AttnArgs), c_vp]),
     "maeclip_attn_bwd": (c_i32, [C.POINTER(AttnArgs), c_vp]),
     "maeclip_ln_fwd": (c_i32, [C.POINTER(LnFwdArgs), c_vp]),
