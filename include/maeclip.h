@@ -698,6 +698,54 @@ typedef struct {
 size_t maeclip_clip_loss_workspace(int64_t N, int64_t P, int64_t grad_rows);
 int32_t maeclip_clip_loss(const maeclip_clip_args* args, void* stream);
 
+/* ---------------------------------------------- InfoNCE and SigLIP losses
+ * The hard-target contrastive losses, fp32, fused and deterministic, with no
+ * N x N matrix in memory (the gradient pass recomputes its logit tiles with
+ * the fma chain of the statistics pass). l_ij = (I_i . T_j) / tau + b, tau as
+ * in maeclip_clip_loss (the by-value field, or expf(*log_temperature)).
+ * kind 0, InfoNCE (b = 0):
+ *   loss = (1/2N) sum_i [lse_j(l_ij) + lse_j(l_ji) - 2 l_ii]
+ *   launches: statistics, combine, gradient (if asked), reduce.
+ * kind 1, SigLIP (z_ij = 2 delta_ij - 1, b = *logit_bias or 0):
+ *   loss = -(1/N) sum_ij log sigma(z_ij l_ij)
+ *   launches: products-and-gradient, reduce.
+ * The embeddings are used as given (normalise first with maeclip_l2_normalize).
+ * I, T, P, strides, loss, row_loss_out (per-row terms, their sum is the loss),
+ * dI, dT and the gradient rows: as in maeclip_clip_args; the loss is always
+ * that of all N rows. 1 <= N <= 262144.
+ * d_log_temperature = -sum dl_ij (l_ij - b) and d_logit_bias = sum dl_ij, both
+ * over the image rows i of the gradient slice and all j (slices of disjoint row
+ * ranges add up to the whole derivative); both need dI and dT,
+ * d_log_temperature needs log_temperature. logit_bias / d_logit_bias: kind 1.
+ * workspace: >= maeclip_contrastive_workspace(N, P, number of gradient rows,
+ * kind) bytes, 16-B aligned: O(N). */
+typedef struct {
+  const float* I;
+  const float* T;
+  int64_t ld_I, ld_T;
+  int64_t N, P;
+  int32_t kind;
+  float temperature;
+  const float* log_temperature;
+  const float* logit_bias;
+  float* loss;
+  float* row_loss_out;
+  float* dI;
+  float* dT;
+  int64_t ld_dI, ld_dT;
+  int64_t grad_row0, grad_rows;
+  float* d_log_temperature;
+  float* d_logit_bias;
+  void* workspace;
+  size_t ws_bytes;
+} maeclip_contrastive_args;
+size_t maeclip_contrastive_workspace(int64_t N, int64_t P, int64_t grad_rows, int32_t kind); /* host only */
+int32_t maeclip_contrastive_loss(const maeclip_contrastive_args* args, void* stream);
+/* backward of maeclip_l2_normalize: dx = (g - y (y . g)) / ||x|| where ||x|| >
+ * eps, g / eps elsewhere; one wave per row, fp32, fixed summation order. */
+int32_t maeclip_l2_normalize_bwd(const float* x, const float* g, float* dx, int64_t M, int64_t P, int64_t ldx,
+                                 int64_t ldg, int64_t lddx, float eps, void* stream);
+
 /* ------------------------------------------------------------ step state
  * Device-resident step counters (model RNG step, optimizer step t) so that a
  * whole training step can be captured once in a HIP graph and replayed. */

@@ -52,6 +52,17 @@ class CLIPModel(nn.Module):
             self.log_temperature = nn.Parameter(torch.tensor([math.log(temperature)], dtype=torch.float32))
         else:
             self.log_temperature = None
+        # config.clip_loss, read once: "soft" (the reference's loss), "infonce" or
+        # "siglip" (contrastive_loss below). Only "siglip" has the bias parameter,
+        # so the state_dict keys of the other two are the same.
+        self.clip_loss = CFG.clip_loss
+        if self.clip_loss not in ("soft", "infonce", "siglip"):
+            raise ValueError(f"config.clip_loss must be 'soft', 'infonce' or 'siglip', got {self.clip_loss!r}")
+        self.normalize_embeddings = bool(CFG.normalize_embeddings)
+        if self.clip_loss == "siglip":
+            self.logit_bias = nn.Parameter(torch.tensor([float(CFG.logit_bias_init)], dtype=torch.float32))
+        else:
+            self.logit_bias = None
         self.mask_ratio = CFG.mask_ratio
         self.mae_weight = CFG.mae_weight
         self.norm_pix_loss = CFG.norm_pix_loss
@@ -168,8 +179,14 @@ class CLIPModel(nn.Module):
                                               dtype=dtype, step_ptr=sc)
         image_embeddings = self.image_projection(feat, seed=seed + 29, step_ptr=sc, bwd_step_ptr=snap)
         text_embeddings = self.text_projection(text_features, seed=seed + 31, step_ptr=sc, bwd_step_ptr=snap)
-        clip = clip_loss(image_embeddings, text_embeddings, self.temperature,
-                         group=self.process_group if world > 1 else None, log_temperature=self.log_temperature)
+        group = self.process_group if world > 1 else None
+        if self.clip_loss == "soft":
+            clip = clip_loss(image_embeddings, text_embeddings, self.temperature, group=group,
+                             log_temperature=self.log_temperature)
+        else:
+            clip = contrastive_loss(image_embeddings, text_embeddings, self.clip_loss, self.temperature, group=group,
+                                    log_temperature=self.log_temperature, logit_bias=self.logit_bias,
+                                    normalize=self.normalize_embeddings)
         loss = clip
         self.last_losses = {"clip": clip.detach()}
         if mae:
@@ -221,6 +238,31 @@ def clip_loss(image_embeddings, text_embeddings, temperature=1.0, group=None, lo
         I, T = all_gather_rows(I, group), all_gather_rows(T, group)
     loss, _, _ = K.clip_loss(I, T, temperature, want_grad=False,
                              log_temperature=None if lt is None else lt.detach())
+    return loss
+
+
+def contrastive_loss(image_embeddings, text_embeddings, kind, temperature=1.0, group=None, log_temperature=None,
+                     logit_bias=None, normalize=True):
+    """InfoNCE (kind "infonce") or SigLIP ("siglip") on the fused fp32 kernels,
+    l_ij = (I_i . T_j) / tau + b. normalize: both embeddings are L2-normalised
+    first (on the local rows, before the data-parallel gather). log_temperature
+    as in clip_loss; logit_bias (f32 [1] device tensor, SigLIP): b."""
+    lt, lb = log_temperature, logit_bias
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad
+                                       for t in (image_embeddings, text_embeddings, lt, lb)):
+        I, T = image_embeddings, text_embeddings
+        if normalize:
+            I, T = Fn.L2NormalizeFn.apply(I), Fn.L2NormalizeFn.apply(T)
+        return Fn.ContrastiveLossFn.apply(I, T, kind, temperature, group, lt, lb)
+    I, T = image_embeddings.contiguous(), text_embeddings.contiguous()
+    if normalize:
+        I, T = K.l2_normalize(I), K.l2_normalize(T)
+    if group is not None:
+        from .distributed import all_gather_rows
+        I, T = all_gather_rows(I, group), all_gather_rows(T, group)
+    loss = K.contrastive_loss(I, T, kind, temperature, want_grad=False,
+                              log_temperature=None if lt is None else lt.detach(),
+                              logit_bias=None if lb is None else lb.detach())[0]
     return loss
 
 

@@ -120,6 +120,14 @@ class ClipArgs(C.Structure):
                 ("workspace", c_vp), ("ws_bytes", c_sz), ("log_temperature", c_vp), ("d_log_temperature", c_vp)]
 
 
+class ContrastiveArgs(C.Structure):
+    _fields_ = [("I", c_vp), ("T", c_vp), ("ld_I", c_i64), ("ld_T", c_i64), ("N", c_i64), ("P", c_i64),
+                ("kind", c_i32), ("temperature", c_f32), ("log_temperature", c_vp), ("logit_bias", c_vp),
+                ("loss", c_vp), ("row_loss_out", c_vp), ("dI", c_vp), ("dT", c_vp),
+                ("ld_dI", c_i64), ("ld_dT", c_i64), ("grad_row0", c_i64), ("grad_rows", c_i64),
+                ("d_log_temperature", c_vp), ("d_logit_bias", c_vp), ("workspace", c_vp), ("ws_bytes", c_sz)]
+
+
 class WgradProblem(C.Structure):
     _fields_ = [("dy", c_vp), ("x", c_vp), ("dw", c_vp), ("N", c_i64), ("K", c_i64), ("ldy", c_i64), ("ldx", c_i64)]
 
@@ -209,6 +217,9 @@ _SIGS = {
     "maeclip_mae_loss_bwd_partial_rows": (c_i32, [c_i32, c_i32]),
     "maeclip_clip_loss_workspace": (c_sz, [c_i64, c_i64, c_i64]),
     "maeclip_clip_loss": (c_i32, [C.POINTER(ClipArgs), c_vp]),
+    "maeclip_contrastive_workspace": (c_sz, [c_i64, c_i64, c_i64, c_i32]),
+    "maeclip_contrastive_loss": (c_i32, [C.POINTER(ContrastiveArgs), c_vp]),
+    "maeclip_l2_normalize_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32, c_vp]),
     "maeclip_counter_add": (c_i32, [c_vp, c_i64, c_vp]),
     "maeclip_counter_add_snap": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
     "maeclip_scalar_axpy": (c_i32, [c_vp, c_vp, C.c_float, c_vp, c_vp]),

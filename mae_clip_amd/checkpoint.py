@@ -18,6 +18,8 @@ With config.learnable_temperature the state_dict has one more key,
 The reference has no such key: a checkpoint saved with the flag off (or a
 reference best.pt) does not load strictly into a model built with the flag on,
 and the other way round -- load it with strict=False and set the parameter.
+config.clip_loss = "siglip" adds `logit_bias` (fp32 [1]) in the same way; the
+keys of "soft" and "infonce" are the same.
 
 For resuming a run this module adds what the bare state_dict cannot carry:
   * the optimizer state (AdamW exp_avg / exp_avg_sq / step, torch.optim format),

@@ -33,6 +33,13 @@ trainable = True
 temperature = 1.0
 learnable_temperature = False   # True: CLIPModel trains log_temperature = ln(temperature) (one fp32 parameter,
                                 # read by the loss kernels on the device); put it in a weight_decay = 0 group
+# contrastive loss: "soft" = the reference's soft-target loss (CLIP.py:34-43, embeddings as they are),
+# "infonce" = the OpenAI-CLIP loss (identity targets, symmetric cross-entropy), "siglip" = the pairwise
+# sigmoid loss with a trained bias b (CLIPModel.logit_bias). The SigLIP paper initialises tau = 0.1
+# (temperature = 0.1) with b = -10; log_temperature and logit_bias belong in a weight_decay = 0 group.
+clip_loss = "soft"
+normalize_embeddings = True     # "infonce" / "siglip": L2-normalise both embeddings first; "soft" never normalises
+logit_bias_init = -10.0         # "siglip": initial b
 
 # image size
 size = 224

@@ -1053,6 +1053,77 @@ class ClipLossFn(torch.autograd.Function):
         return dI, dT, None, None, dth
 
 
+class ContrastiveLossFn(torch.autograd.Function):
+    """InfoNCE / SigLIP on the fused fp32 kernels (K.contrastive_loss), wired as
+    ClipLossFn: the same gather and gradient-row slice under data parallelism,
+    the gradients out of the forward's call, the backward only scales them by
+    grad_output. d theta and d b (sums over the rank's own rows) go into the
+    parameters' gradient slots."""
+
+    @staticmethod
+    def forward(ctx, I, T, kind, temperature, group=None, log_temperature=None, logit_bias=None):
+        I = I.contiguous()
+        T = T.contiguous()
+        rows = None
+        if group is not None:
+            from .distributed import all_gather_rows, world_rank, check_equal_rows
+            world, rank = world_rank(group)
+            if world > 1:
+                B = I.shape[0]
+                check_equal_rows(B, group, I.device)
+                I = all_gather_rows(I, group)
+                T = all_gather_rows(T, group)
+                rows = (rank * B, B)
+        lt = None if log_temperature is None else log_temperature.detach()
+        lb = None if logit_bias is None else logit_bias.detach()
+        ctx.theta = log_temperature if lt is not None and ctx.needs_input_grad[5] else None
+        ctx.bias = logit_bias if lb is not None and ctx.needs_input_grad[6] else None
+        out = K.contrastive_loss(I, T, kind, temperature, want_grad=True, grad_rows=rows, log_temperature=lt,
+                                 logit_bias=lb, want_dtemp=ctx.theta is not None, want_dbias=ctx.bias is not None)
+        ctx.grads = out[1:]
+        ctx.arena = _arena()
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, gl):
+        grads = list(ctx.grads)
+        ctx.grads = None
+        s = gl.reshape(1).contiguous()
+        dI, dT = grads[0], grads[1]
+        if ctx.theta is None and ctx.bias is None:
+            # scaled in place by the device grad_output: one launch, no host sync
+            K.scale_by_scalar(s, 1.0, dI, dT, dI, dT)
+            return dI, dT, None, None, None, None, None
+        # dI, dT are the halves of one buffer: scaled in place as one tensor, and
+        # the first scalar gradient into its parameter's slot in the same launch
+        both = dI._base.view(-1)
+        scalars = grads[2:]
+        dth = db = None
+        if ctx.theta is not None:
+            _, dth = K.scale_by_scalar(s, 1.0, both, scalars.pop(0), both, gout(ctx.arena, ctx.theta))
+            if ctx.bias is not None:
+                db, _ = K.scale_by_scalar(s, 1.0, scalars.pop(0), None, gout(ctx.arena, ctx.bias))
+        else:
+            _, db = K.scale_by_scalar(s, 1.0, both, scalars.pop(0), both, gout(ctx.arena, ctx.bias))
+        return dI, dT, None, None, None, dth, db
+
+
+class L2NormalizeFn(torch.autograd.Function):
+    """y = x / max(||x||, eps) row-wise (F.normalize) on the fp32 kernels."""
+
+    @staticmethod
+    def forward(ctx, x, eps=1e-12):
+        x = x.contiguous()
+        ctx.save_for_backward(x)
+        ctx.eps = float(eps)
+        return K.l2_normalize(x, eps)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        return K.l2_normalize_bwd(x, g.contiguous(), ctx.eps), None
+
+
 class CombineLossFn(torch.autograd.Function):
     """loss = clip + w * mae on device scalars (one launch; backward: grad_output
     to the CLIP term as is, w * grad_output to the MAE term in one launch)."""

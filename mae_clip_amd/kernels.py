@@ -805,6 +805,86 @@ def clip_loss(I, T, temperature, want_grad=True, grad_rows=None, row_loss=False,
     return out
 
 
+INFONCE, SIGLIP = 0, 1
+CONTRASTIVE_KINDS = {"infonce": INFONCE, "siglip": SIGLIP}
+
+
+def contrastive_loss(I, T, kind, temperature, want_grad=True, grad_rows=None, row_loss=False, log_temperature=None,
+                     logit_bias=None, want_dtemp=False, want_dbias=False):
+    """Fused InfoNCE (kind "infonce" / 0) or SigLIP ("siglip" / 1) loss on the
+    embeddings as given, l_ij = (I_i . T_j) / tau + b; no N x N matrix is stored.
+    grad_rows, log_temperature, want_dtemp: as in clip_loss. logit_bias (device
+    f32 [1], SigLIP only): b, 0 when None; want_dbias (needs want_grad):
+    d loss / d b of the gradient rows as a device f32 [1] tensor.
+    Returns (loss, dI, dT[, rl][, dtheta][, dbias]); with want_dtemp or
+    want_dbias dI and dT are the two halves of one buffer (dI._base)."""
+    _dev(I, T)
+    kind = CONTRASTIVE_KINDS.get(kind, kind)
+    if kind not in (INFONCE, SIGLIP):
+        raise ValueError(f"contrastive_loss: kind must be 'infonce' or 'siglip', got {kind!r}")
+    N, P = I.shape
+    r0, nr = (0, N) if grad_rows is None else grad_rows
+    if not (0 <= r0 and nr >= 1 and r0 + nr <= N):
+        raise ValueError(f"contrastive_loss: gradient rows {grad_rows} out of range for N={N}")
+    for name, t in (("log_temperature", log_temperature), ("logit_bias", logit_bias)):
+        if t is not None:
+            _dev(t)
+            if t.dtype != torch.float32 or t.numel() != 1:
+                raise ValueError(f"contrastive_loss: {name} must be one f32 element")
+    if logit_bias is not None and kind != SIGLIP:
+        raise ValueError("contrastive_loss: logit_bias is SigLIP's only")
+    if want_dtemp and (log_temperature is None or not want_grad):
+        raise ValueError("contrastive_loss: want_dtemp needs log_temperature and want_grad")
+    if want_dbias and (kind != SIGLIP or not want_grad):
+        raise ValueError("contrastive_loss: want_dbias needs SigLIP and want_grad")
+    ws_bytes = int(L.lib().maeclip_contrastive_workspace(N, P, nr if want_grad else 0, kind))
+    ws = torch.empty((max(ws_bytes // 4, 4),), device=I.device, dtype=torch.float32)
+    loss = torch.empty((), device=I.device, dtype=torch.float32)
+    if want_dtemp or want_dbias:
+        dI, dT = torch.empty((2, nr, P), device=I.device, dtype=torch.float32).unbind(0)
+    else:
+        dI = torch.empty((nr, P), device=I.device, dtype=torch.float32) if want_grad else None
+        dT = torch.empty((nr, P), device=I.device, dtype=torch.float32) if want_grad else None
+    rl = torch.empty((N,), device=I.device, dtype=torch.float32) if row_loss else None
+    dth = torch.empty((1,), device=I.device, dtype=torch.float32) if want_dtemp else None
+    db = torch.empty((1,), device=I.device, dtype=torch.float32) if want_dbias else None
+    a = L.ContrastiveArgs(I=I.data_ptr(), T=T.data_ptr(), ld_I=I.stride(0), ld_T=T.stride(0), N=N, P=P, kind=kind,
+                          temperature=float(temperature), log_temperature=_ptr(log_temperature),
+                          logit_bias=_ptr(logit_bias), loss=loss.data_ptr(), row_loss_out=_ptr(rl), dI=_ptr(dI),
+                          dT=_ptr(dT), ld_dI=P, ld_dT=P, grad_row0=r0, grad_rows=nr, d_log_temperature=_ptr(dth),
+                          d_logit_bias=_ptr(db), workspace=ws.data_ptr(), ws_bytes=ws_bytes)
+    _call("maeclip_contrastive_loss", C.byref(a), _stream())
+    return (loss, dI, dT) + ((rl,) if row_loss else ()) + ((dth,) if want_dtemp else ()) + ((db,) if want_dbias else ())
+
+
+def _rows_f32(x, what):
+    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError(f"{what}: fp32 [M, P] with unit column stride expected")
+
+
+def l2_normalize(x, eps=1e-12):
+    """F.normalize(x, p=2, dim=-1) for fp32 [M, P] rows (any row stride)."""
+    _dev(x)
+    _rows_f32(x, "l2_normalize")
+    y = torch.empty((x.shape[0], x.shape[1]), device=x.device, dtype=torch.float32)
+    _call("maeclip_l2_normalize", x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1], x.stride(0), y.stride(0),
+          float(eps), _stream())
+    return y
+
+
+def l2_normalize_bwd(x, g, eps=1e-12):
+    """Gradient of l2_normalize at x for the output gradient g (both fp32 [M, P])."""
+    _dev(x, g)
+    _rows_f32(x, "l2_normalize_bwd")
+    _rows_f32(g, "l2_normalize_bwd")
+    if g.shape != x.shape:
+        raise ValueError("l2_normalize_bwd: x and g must have one shape")
+    dx = torch.empty((x.shape[0], x.shape[1]), device=x.device, dtype=torch.float32)
+    _call("maeclip_l2_normalize_bwd", x.data_ptr(), g.data_ptr(), dx.data_ptr(), x.shape[0], x.shape[1], x.stride(0),
+          g.stride(0), dx.stride(0), float(eps), _stream())
+    return dx
+
+
 # ------------------------------------------------------------ multi-tensor
 def counter_add_snap(counter, snap, delta=1):
     """snap[0] = counter[0]; counter[0] += delta (stream-ordered, one launch)."""
