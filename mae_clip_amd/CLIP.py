@@ -221,24 +221,27 @@ class CLIPModel(nn.Module):
         return loss
 
 
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def _loss_only(kernel, I, T, group, *args, **scalars):
+    """The no-grad path of both losses: gather, then the kernel's loss alone."""
+    I, T, _ = Fn.gather_pair(I, T, group)
+    return kernel(I, T, *args, want_grad=False, **{k: None if t is None else t.detach() for k, t in scalars.items()})[0]
+
+
 def clip_loss(image_embeddings, text_embeddings, temperature=1.0, group=None, log_temperature=None):
     """CLIP.py:34-43 on the fused fp32 kernel (group: data-parallel gather).
     log_temperature (f32 [1] device tensor, theta = ln tau): the kernel takes
     tau = exp(theta) from it, with or without autograd, and `temperature` is
     not used."""
     lt = log_temperature
-    if torch.is_grad_enabled() and (image_embeddings.requires_grad or text_embeddings.requires_grad
-                                    or (lt is not None and lt.requires_grad)):
+    if _wants_grad(image_embeddings, text_embeddings, lt):
         if lt is None:
             return Fn.ClipLossFn.apply(image_embeddings, text_embeddings, temperature, group)
         return Fn.ClipLossFn.apply(image_embeddings, text_embeddings, temperature, group, lt)
-    I, T = image_embeddings.contiguous(), text_embeddings.contiguous()
-    if group is not None:
-        from .distributed import all_gather_rows
-        I, T = all_gather_rows(I, group), all_gather_rows(T, group)
-    loss, _, _ = K.clip_loss(I, T, temperature, want_grad=False,
-                             log_temperature=None if lt is None else lt.detach())
-    return loss
+    return _loss_only(K.clip_loss, image_embeddings, text_embeddings, group, temperature, log_temperature=lt)
 
 
 def contrastive_loss(image_embeddings, text_embeddings, kind, temperature=1.0, group=None, log_temperature=None,
@@ -248,22 +251,14 @@ def contrastive_loss(image_embeddings, text_embeddings, kind, temperature=1.0, g
     first (on the local rows, before the data-parallel gather). log_temperature
     as in clip_loss; logit_bias (f32 [1] device tensor, SigLIP): b."""
     lt, lb = log_temperature, logit_bias
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad
-                                       for t in (image_embeddings, text_embeddings, lt, lb)):
-        I, T = image_embeddings, text_embeddings
+    I, T = image_embeddings, text_embeddings
+    if _wants_grad(I, T, lt, lb):
         if normalize:
             I, T = Fn.L2NormalizeFn.apply(I), Fn.L2NormalizeFn.apply(T)
         return Fn.ContrastiveLossFn.apply(I, T, kind, temperature, group, lt, lb)
-    I, T = image_embeddings.contiguous(), text_embeddings.contiguous()
     if normalize:
-        I, T = K.l2_normalize(I), K.l2_normalize(T)
-    if group is not None:
-        from .distributed import all_gather_rows
-        I, T = all_gather_rows(I, group), all_gather_rows(T, group)
-    loss = K.contrastive_loss(I, T, kind, temperature, want_grad=False,
-                              log_temperature=None if lt is None else lt.detach(),
-                              logit_bias=None if lb is None else lb.detach())[0]
-    return loss
+        I, T = K.l2_normalize(I.contiguous()), K.l2_normalize(T.contiguous())
+    return _loss_only(K.contrastive_loss, I, T, group, kind, temperature, log_temperature=lt, logit_bias=lb)
 
 
 def cross_entropy(preds, targets, reduction="none"):

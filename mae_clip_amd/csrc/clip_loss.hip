@@ -43,15 +43,13 @@
 // so that row statistics over j are lane-local. In the later passes lane
 // (i = lane & 15, j = 4 (lane >> 4) + r) reads its four consecutive j of row i
 // of a stored matrix as one 16-B load: the B-operand layout of the contraction.
-// MFMA k mapping: in sub-step s of k-group b, hardware k = lane>>4 carries real
-// k = 16b + 4(lane>>4) + s, so each lane reads its operands as 16-byte vectors.
-#include "common.h"
+// The dot tile and its MFMA k mapping, the online (max, sumexp) merge and tau
+// of the call are simtile.h's, shared with contrastive.hip and retrieval_eval.hip.
+#include "simtile.h"
 #include "../../include/maeclip.h"
 
 namespace {
-typedef float v2f __attribute__((ext_vector_type(2)));
 constexpr int NT = 256;
-constexpr float NEG = -1.0e30f;
 
 struct ClipK {
   const float* I;
@@ -70,28 +68,9 @@ struct ClipK {
   float* dtrow;        // [16 * gradient row blocks]: per-row terms of d loss / d theta
 };
 
-__device__ __forceinline__ v4f mma4(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// tau of the call: the by-value field, or exp(theta) of the device theta. The one
-// expression every kernel takes it from, so that the stored matrices and the
-// gradient use the same value bit for bit (exp(0) = 1 exactly: theta = 0 is the
-// by-value tau = 1). Wave-uniform, and back in a scalar register after the exp.
-__device__ __forceinline__ float clip_tau(const ClipK& a) {
-  if (!a.ltau) return a.tau;
-  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(expf(*a.ltau))));
-}
-
-__device__ __forceinline__ void merge_ms(float& m, float& s, float m2, float s2) {
-  const float M = fmaxf(m, m2);
-  s = s * __expf(m - M) + s2 * __expf(m2 - M);
-  m = M;
-}
-
 // (max, log sumexp) from partials [js * stride + idx] (max, sumexp pairs), js <
-// n, read 16 at a time with every load in flight. The two parts stay separate:
-// lse = M + log z rounded to f32 is off by up to ulp(|M|) / 2 (1e-6 at |x| ~ 30),
-// which the nearly cancelling gradient terms then amplify; x - lse is taken as
-// (x - M) - log z, both exact or small where it matters.
+// n, read 16 at a time with every load in flight. The two parts stay separate
+// for lsub().
 __device__ __forceinline__ void lse_parts(const float* part, int64_t stride, int64_t idx, int n, float& M, float& lz) {
   M = NEG;
   float z = 0.f;
@@ -105,7 +84,6 @@ __device__ __forceinline__ void lse_parts(const float* part, int64_t stride, int
   }
   lz = logf(z);
 }
-__device__ __forceinline__ float lsub(float x, float M, float lz) { return (x - M) - lz; }
 
 // i-side B operand of wave role ty: rows i0 + (lane&15), 16-B vector b at k = 16b + 4(lane>>4)
 template <int NB>
@@ -153,16 +131,7 @@ template <int NB>
 __device__ __forceinline__ v4f score_tile(const float* Xj, int ty, const v4f (&ir)[4 * NB], int lane) {
   constexpr int RS = 64 * NB + 4;
   const float* rowp = Xj + ((ty & 1) * 16 + (lane & 15)) * RS + 4 * (lane >> 4);
-  v4f c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int b = 0; b < 4 * NB; ++b) {
-    const v4f x = *(const v4f*)(rowp + 16 * b);
-    c0 = mma4(x[0], ir[b][0], c0);
-    c1 = mma4(x[1], ir[b][1], c1);
-    c0 = mma4(x[2], ir[b][2], c0);
-    c1 = mma4(x[3], ir[b][3], c1);
-  }
-  return c0 + c1;
+  return dot_tile<4 * NB>(rowp, ir);
 }
 
 // ------------------------------------------------------------------ products
@@ -177,7 +146,7 @@ __global__ void __launch_bounds__(NT) clip_products_kernel(const ClipK a) {
   const int js = blockIdx.y;
   const int jt0 = js * a.nrep, njt = (a.N + 15) / 16;
   const int jt1 = min(jt0 + a.nrep, njt);
-  const float tau = clip_tau(a), itau = 1.f / tau;
+  const float tau = call_tau(a), itau = 1.f / tau;
   const int N = a.N;
 
   v4f ir[4 * NB];
@@ -334,7 +303,7 @@ __global__ void __launch_bounds__(NT) clip_grad_kernel(const ClipK a, float* los
   const int lane = threadIdx.x & 63, g = lane >> 4, il = lane & 15;
   const int w = threadIdx.x >> 6;
   const int N = a.N;
-  const float tau = clip_tau(a), itau = 1.f / tau, inv2n = 0.5f / (float)N;
+  const float tau = call_tau(a), itau = 1.f / tau, inv2n = 0.5f / (float)N;
   const float* st = a.stat;   // [8][N]: mS, zS, mR, zR, mC, zC, c, rl
   const float* rlv = a.stat + 7LL * N;
   if (blockIdx.x == 0 && blockIdx.y == 0) {
@@ -532,28 +501,15 @@ extern "C" size_t maeclip_clip_loss_workspace(int64_t N, int64_t P, int64_t grad
 
 extern "C" int32_t maeclip_clip_loss(const maeclip_clip_args* a, void* stream) {
   MC_CHECK_ARG(a && a->I && a->T && a->loss && a->workspace, "maeclip_clip_loss: null pointer");
-  MC_CHECK_ARG(a->N > 0 && a->N <= 16384, "maeclip_clip_loss: N must be in [1, 16384] (got %lld)", (long long)a->N);
-  MC_CHECK_ARG(a->P == 64 || a->P == 128 || a->P == 256 || a->P == 512,
-               "maeclip_clip_loss: P must be 64, 128, 256 or 512 (got %lld)", (long long)a->P);
-  MC_CHECK_ARG(a->log_temperature || a->temperature > 0.f, "maeclip_clip_loss: temperature must be > 0");
+  if (pair_check_shape(a, "maeclip_clip_loss", 16384)) return -1;
   MC_CHECK_ARG(((uintptr_t)a->log_temperature & 3) == 0 && ((uintptr_t)a->d_log_temperature & 3) == 0,
                "maeclip_clip_loss: log_temperature / d_log_temperature must be 4-byte aligned");
   MC_CHECK_ARG(!a->d_log_temperature || (a->log_temperature && a->dI && a->dT),
                "maeclip_clip_loss: d_log_temperature needs log_temperature, dI and dT");
-  const int64_t ldi = a->ld_I ? a->ld_I : a->P, ldt = a->ld_T ? a->ld_T : a->P;
-  MC_CHECK_ARG(ldi >= a->P && ldt >= a->P && ldi % 4 == 0 && ldt % 4 == 0 && ((uintptr_t)a->I & 15) == 0 &&
-                   ((uintptr_t)a->T & 15) == 0,
-               "maeclip_clip_loss: I/T rows must be 16-byte aligned");
-  const bool grad = a->dI && a->dT;
-  int64_t gr = 0;
-  if (grad) {
-    MC_CHECK_ARG(a->grad_row0 >= 0 && a->grad_row0 < a->N && a->grad_rows >= 0 && a->grad_row0 + a->grad_rows <= a->N,
-                 "maeclip_clip_loss: gradient rows out of range");
-    gr = a->grad_rows > 0 ? a->grad_rows : a->N - a->grad_row0;
-    const int64_t lddi = a->ld_dI ? a->ld_dI : a->P, lddt = a->ld_dT ? a->ld_dT : a->P;
-    MC_CHECK_ARG(lddi % 4 == 0 && lddt % 4 == 0 && ((uintptr_t)a->dI & 15) == 0 && ((uintptr_t)a->dT & 15) == 0,
-                 "maeclip_clip_loss: dI/dT rows must be 16-byte aligned");
-  }
+  // dI/dT rows shorter than P pass here (full_rows = false), and one of dI/dT
+  // alone means no gradient: both unlike maeclip_contrastive_loss
+  int64_t gr;
+  if (pair_check_rows(a, "maeclip_clip_loss", false, &gr)) return -1;
   MC_CHECK_ARG(a->ws_bytes >= maeclip_clip_loss_workspace(a->N, a->P, gr) && ((uintptr_t)a->workspace & 15) == 0,
                "maeclip_clip_loss: workspace too small or misaligned");
   hipStream_t s = (hipStream_t)stream;

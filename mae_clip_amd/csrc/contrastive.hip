@@ -39,18 +39,16 @@
 //           the products alone and write the row's loss term.
 //   reduce  one workgroup: loss = sum of the row terms, d theta, d b (double,
 //           fixed order).
-// MFMA k mapping as in clip_loss.hip: in sub-step s of k-group b, hardware k =
-// lane>>4 carries real k = 16b + 4(lane>>4) + s, so each lane reads its
-// operands as 16-byte vectors. The workgroup's own 16 rows X_i sit in LDS
-// (row stride P + 4), the Y_j rows are read from global memory.
-#include "common.h"
+// The dot tile and its MFMA k mapping, the online (max, sumexp) merge and tau
+// and b of the call are simtile.h's, shared with clip_loss.hip and
+// retrieval_eval.hip. The workgroup's own 16 rows X_i sit in LDS (row stride
+// P + 4), the Y_j rows are read from global memory.
+#include "simtile.h"
 #include "../../include/maeclip.h"
 
 namespace {
-typedef float v2f __attribute__((ext_vector_type(2)));
 constexpr int NT = 256;
 constexpr int NW = NT / 64;
-constexpr float NEG = -1.0e30f;
 constexpr int64_t MAX_N = 262144;
 
 struct ConK {
@@ -70,26 +68,6 @@ struct ConK {
   int g0, Ng, ngb;     // gradient rows, gradient row blocks
 };
 
-__device__ __forceinline__ v4f mma4(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// tau of the call, exactly as clip_tau() of clip_loss.hip: the by-value field,
-// or exp(theta) of the device theta (exp(0) = 1 exactly).
-__device__ __forceinline__ float con_tau(const ConK& a) {
-  if (!a.ltau) return a.tau;
-  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(expf(*a.ltau))));
-}
-__device__ __forceinline__ float con_bias(const ConK& a) {
-  if (!a.bias) return 0.f;
-  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(*a.bias)));
-}
-
-__device__ __forceinline__ void merge_ms(float& m, float& s, float m2, float s2) {
-  const float M = fmaxf(m, m2);
-  s = s * __expf(m - M) + s2 * __expf(m2 - M);
-  m = M;
-}
-__device__ __forceinline__ float lsub(float x, float M, float lz) { return (x - M) - lz; }
-
 // the workgroup's 16 rows of X from row i0 -> LDS [16][P + 4] (zero rows past N)
 template <int NB>
 __device__ __forceinline__ void stage_rows(const float* X, int64_t ld, int i0, int N, float* Xi) {
@@ -103,23 +81,15 @@ __device__ __forceinline__ void stage_rows(const float* X, int64_t ld, int i0, i
 
 // 16x16 dot tile D[j = 4(lane>>4) + reg][i = lane&15] = Y_j . X_i; yrow: the
 // lane's row j = jb + (lane&15) of Y (clamped by the caller) + 4(lane>>4); xi:
-// the lane's row of the LDS image + 4(lane>>4). Two accumulator chains, one
-// order: the statistics pass and the gradient pass get the same bits.
+// the lane's row of the LDS image + 4(lane>>4). Every global load of the Y row
+// is issued before the first MFMA. The statistics pass and the gradient pass
+// call this, so both get the same bits.
 template <int NB>
-__device__ __forceinline__ v4f dot_tile(const float* yrow, const float* xi) {
+__device__ __forceinline__ v4f yx_tile(const float* yrow, const float* xi) {
   v4f y[4 * NB];
 #pragma unroll
   for (int b = 0; b < 4 * NB; ++b) y[b] = *(const v4f*)(yrow + 16 * b);
-  v4f c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int b = 0; b < 4 * NB; ++b) {
-    const v4f x = *(const v4f*)(xi + 16 * b);
-    c0 = mma4(y[b][0], x[0], c0);
-    c1 = mma4(y[b][1], x[1], c1);
-    c0 = mma4(y[b][2], x[2], c0);
-    c1 = mma4(y[b][3], x[3], c1);
-  }
-  return c0 + c1;
+  return dot_tile<4 * NB>(y, xi);
 }
 
 // ------------------------------------------------------------------ stats
@@ -137,14 +107,14 @@ __global__ void __launch_bounds__(NT) con_stats_kernel(const ConK a) {
   const int64_t ldY = a.ld[1 - role];
   stage_rows<NB>(a.X[role], a.ld[role], i0, N, Xi);
   __syncthreads();
-  const float itau = 1.f / con_tau(a);
+  const float itau = 1.f / call_tau(a);
   const int njt = (N + 15) / 16;
   const int jt0 = (int)blockIdx.y * a.nrep, jt1 = min(jt0 + a.nrep, njt);
   const int i = i0 + il;
   float m0 = NEG, s0 = 0.f;
   for (int jt = jt0 + w; jt < jt1; jt += NW) {
     const int jb = 16 * jt;
-    const v4f d = dot_tile<NB>(Y + (int64_t)min(jb + il, N - 1) * ldY + 4 * g, Xi + il * RS + 4 * g);
+    const v4f d = yx_tile<NB>(Y + (int64_t)min(jb + il, N - 1) * ldY + 4 * g, Xi + il * RS + 4 * g);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int j = jb + 4 * g + r;
@@ -214,7 +184,7 @@ __global__ void __launch_bounds__(NT) con_grad_kernel(const ConK a, float* G0, i
   const int64_t ldY = a.ld[1 - role];
   stage_rows<NB>(a.X[role], a.ld[role], i0, N, Xi);
   __syncthreads();
-  const float itau = 1.f / con_tau(a), b = con_bias(a);
+  const float itau = 1.f / call_tau(a), b = call_scalar(a.bias);
   const bool sig = a.kind == 1;
   const int i = i0 + il;
   const bool iok = i < iend;
@@ -235,7 +205,7 @@ __global__ void __launch_bounds__(NT) con_grad_kernel(const ConK a, float* G0, i
   float lsum = 0.f, tsum = 0.f, usum = 0.f;
   for (int jt = w; jt < njt; jt += NW) {
     const int jb = 16 * jt;
-    const v4f d = dot_tile<NB>(Y + (int64_t)min(jb + il, N - 1) * ldY + 4 * g, Xi + il * RS + 4 * g);
+    const v4f d = yx_tile<NB>(Y + (int64_t)min(jb + il, N - 1) * ldY + 4 * g, Xi + il * RS + 4 * g);
     float wv[4];
     const float* yc[4];
 #pragma unroll
@@ -351,37 +321,6 @@ __global__ void __launch_bounds__(NT) con_reduce_kernel(const float* __restrict_
   }
 }
 
-// one wave per row: backward of y = x / max(||x||, eps). ||x||^2 is summed in
-// the forward's order (retrieval.hip), so the branch taken is the forward's.
-__global__ void __launch_bounds__(NT) l2_normalize_bwd_kernel(const float* __restrict__ x, const float* __restrict__ gy,
-                                                              float* __restrict__ dx, int64_t M, int64_t P, int64_t ldx,
-                                                              int64_t ldg, int64_t lddx, float eps) {
-  const int64_t row = (int64_t)blockIdx.x * NW + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= M) return;
-  const float* xr = x + row * ldx;
-  const float* gr = gy + row * ldg;
-  float ss = 0.f, dot = 0.f;
-  for (int64_t c = lane; c < P; c += 64) {
-    ss = fmaf(xr[c], xr[c], ss);
-    dot = fmaf(xr[c], gr[c], dot);
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    ss += __shfl_xor(ss, o, 64);
-    dot += __shfl_xor(dot, o, 64);
-  }
-  const float nrm = sqrtf(ss);
-  float* dr = dx + row * lddx;
-  if (nrm > eps) {
-    // dx = (g - y (y . g)) / ||x||, y = x / ||x||
-    const float inv = 1.f / nrm, yg = dot * inv;
-    for (int64_t c = lane; c < P; c += 64) dr[c] = (gr[c] - (xr[c] * inv) * yg) * inv;
-  } else {
-    for (int64_t c = lane; c < P; c += 64) dr[c] = gr[c] / eps;
-  }
-}
-
 // ------------------------------------------------------------ geometry
 int64_t up4(int64_t n) { return (n + 3) / 4 * 4; }
 
@@ -486,11 +425,7 @@ extern "C" int32_t maeclip_contrastive_loss(const maeclip_contrastive_args* a, v
   MC_CHECK_ARG(a && a->I && a->T && a->loss && a->workspace, "maeclip_contrastive_loss: null pointer");
   MC_CHECK_ARG(a->kind == 0 || a->kind == 1, "maeclip_contrastive_loss: kind must be 0 (InfoNCE) or 1 (SigLIP) (got %d)",
                (int)a->kind);
-  MC_CHECK_ARG(a->N > 0 && a->N <= MAX_N, "maeclip_contrastive_loss: N must be in [1, %lld] (got %lld)", (long long)MAX_N,
-               (long long)a->N);
-  MC_CHECK_ARG(a->P == 64 || a->P == 128 || a->P == 256 || a->P == 512,
-               "maeclip_contrastive_loss: P must be 64, 128, 256 or 512 (got %lld)", (long long)a->P);
-  MC_CHECK_ARG(a->log_temperature || a->temperature > 0.f, "maeclip_contrastive_loss: temperature must be > 0");
+  if (pair_check_shape(a, "maeclip_contrastive_loss", MAX_N)) return -1;
   MC_CHECK_ARG(a->kind == 1 || (!a->logit_bias && !a->d_logit_bias),
                "maeclip_contrastive_loss: logit_bias / d_logit_bias are SigLIP's (kind 1) only");
   MC_CHECK_ARG(((uintptr_t)a->log_temperature & 3) == 0 && ((uintptr_t)a->d_log_temperature & 3) == 0 &&
@@ -500,21 +435,8 @@ extern "C" int32_t maeclip_contrastive_loss(const maeclip_contrastive_args* a, v
                "maeclip_contrastive_loss: d_log_temperature needs log_temperature, dI and dT");
   MC_CHECK_ARG(!a->d_logit_bias || (a->dI && a->dT), "maeclip_contrastive_loss: d_logit_bias needs dI and dT");
   MC_CHECK_ARG(!a->dI == !a->dT, "maeclip_contrastive_loss: dI and dT come together");
-  const int64_t ldi = a->ld_I ? a->ld_I : a->P, ldt = a->ld_T ? a->ld_T : a->P;
-  MC_CHECK_ARG(ldi >= a->P && ldt >= a->P && ldi % 4 == 0 && ldt % 4 == 0 && ((uintptr_t)a->I & 15) == 0 &&
-                   ((uintptr_t)a->T & 15) == 0,
-               "maeclip_contrastive_loss: I/T rows must be 16-byte aligned");
-  const bool grad = a->dI && a->dT;
-  int64_t gr = 0;
-  if (grad) {
-    MC_CHECK_ARG(a->grad_row0 >= 0 && a->grad_row0 < a->N && a->grad_rows >= 0 && a->grad_row0 + a->grad_rows <= a->N,
-                 "maeclip_contrastive_loss: gradient rows out of range");
-    gr = a->grad_rows > 0 ? a->grad_rows : a->N - a->grad_row0;
-    const int64_t lddi = a->ld_dI ? a->ld_dI : a->P, lddt = a->ld_dT ? a->ld_dT : a->P;
-    MC_CHECK_ARG(lddi >= a->P && lddt >= a->P && lddi % 4 == 0 && lddt % 4 == 0 && ((uintptr_t)a->dI & 15) == 0 &&
-                     ((uintptr_t)a->dT & 15) == 0,
-                 "maeclip_contrastive_loss: dI/dT rows must be 16-byte aligned");
-  }
+  int64_t gr;
+  if (pair_check_rows(a, "maeclip_contrastive_loss", true, &gr)) return -1;
   MC_CHECK_ARG(a->ws_bytes >= maeclip_contrastive_workspace(a->N, a->P, gr, a->kind) && ((uintptr_t)a->workspace & 15) == 0,
                "maeclip_contrastive_loss: workspace too small or misaligned");
   hipStream_t s = (hipStream_t)stream;
@@ -524,15 +446,4 @@ extern "C" int32_t maeclip_contrastive_loss(const maeclip_contrastive_args* a, v
     case 256: return run<4>(*a, gr, s);
     default: return run<8>(*a, gr, s);
   }
-}
-
-extern "C" int32_t maeclip_l2_normalize_bwd(const float* x, const float* g, float* dx, int64_t M, int64_t P, int64_t ldx,
-                                            int64_t ldg, int64_t lddx, float eps, void* stream) {
-  MC_CHECK_ARG(x && g && dx && M >= 0 && P > 0 && ldx >= P && ldg >= P && lddx >= P && eps > 0.f,
-               "maeclip_l2_normalize_bwd: bad arguments");
-  if (M == 0) return 0;
-  hipLaunchKernelGGL(l2_normalize_bwd_kernel, dim3((unsigned)((M + NW - 1) / NW)), dim3(NT), 0, (hipStream_t)stream, x, g,
-                     dx, M, P, ldx, ldg, lddx, eps);
-  MC_CHECK_LAUNCH("maeclip_l2_normalize_bwd");
-  return 0;
 }

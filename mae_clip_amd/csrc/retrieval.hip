@@ -5,12 +5,15 @@
 //   _, indices         = torch.topk(dot_similarity.squeeze(0), n * 5)
 // maeclip_l2_normalize: one wave per row, x / max(||x||_2, eps) (F.normalize's
 // clamp_min(eps) semantics), fp32, fixed summation order.
+// maeclip_l2_normalize_bwd: its gradient, one wave per row; ||x||^2 comes from
+// the forward's own sum (row_dots of simtile.h), so both take the same branch
+// at the eps clamp.
 // maeclip_topk_rows: one workgroup per row; k selection rounds, each a block
 // arg-max over the row restricted to entries after the previous pick in the
 // order (value descending, index ascending): sorted output, ties broken by the
 // lower index, deterministic. The row is re-read from L2 every round
 // (k <= 1024; the retrieval case is k = 45 over <= 1e5 candidates).
-#include "common.h"
+#include "simtile.h"
 #include "../../include/maeclip.h"
 
 namespace {
@@ -22,13 +25,35 @@ __global__ void __launch_bounds__(256) l2_normalize_kernel(const float* __restri
   const int lane = threadIdx.x & 63;
   if (row >= M) return;
   const float* xr = x + row * ldx;
-  float ss = 0.f;
-  for (int64_t c = lane; c < P; c += 64) ss = fmaf(xr[c], xr[c], ss);
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o, 64);
-  const float nrm = fmaxf(sqrtf(ss), eps);
+  const float* const with[1] = {xr};
+  float ss[1];
+  row_dots(xr, with, P, lane, ss);
+  const float nrm = fmaxf(sqrtf(ss[0]), eps);
   float* yr = y + row * ldy;
   for (int64_t c = lane; c < P; c += 64) yr[c] = xr[c] / nrm;
+}
+
+// one wave per row: backward of y = x / max(||x||, eps), on the forward's ||x||^2
+__global__ void __launch_bounds__(256) l2_normalize_bwd_kernel(const float* __restrict__ x, const float* __restrict__ gy,
+                                                               float* __restrict__ dx, int64_t M, int64_t P, int64_t ldx,
+                                                               int64_t ldg, int64_t lddx, float eps) {
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= M) return;
+  const float* xr = x + row * ldx;
+  const float* gr = gy + row * ldg;
+  const float* const with[2] = {xr, gr};
+  float s[2];   // ||x||^2, x . g
+  row_dots(xr, with, P, lane, s);
+  const float nrm = sqrtf(s[0]);
+  float* dr = dx + row * lddx;
+  if (nrm > eps) {
+    // dx = (g - y (y . g)) / ||x||, y = x / ||x||
+    const float inv = 1.f / nrm, yg = s[1] * inv;
+    for (int64_t c = lane; c < P; c += 64) dr[c] = (gr[c] - (xr[c] * inv) * yg) * inv;
+  } else {
+    for (int64_t c = lane; c < P; c += 64) dr[c] = gr[c] / eps;
+  }
 }
 
 // is (v, i) ranked before (bv, bi)?  value descending, index ascending
@@ -95,6 +120,17 @@ extern "C" int32_t maeclip_l2_normalize(const float* x, float* y, int64_t M, int
   hipLaunchKernelGGL(l2_normalize_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, y, M,
                      P, ldx, ldy, eps);
   MC_CHECK_LAUNCH("maeclip_l2_normalize");
+  return 0;
+}
+
+extern "C" int32_t maeclip_l2_normalize_bwd(const float* x, const float* g, float* dx, int64_t M, int64_t P, int64_t ldx,
+                                            int64_t ldg, int64_t lddx, float eps, void* stream) {
+  MC_CHECK_ARG(x && g && dx && M >= 0 && P > 0 && ldx >= P && ldg >= P && lddx >= P && eps > 0.f,
+               "maeclip_l2_normalize_bwd: bad arguments");
+  if (M == 0) return 0;
+  hipLaunchKernelGGL(l2_normalize_bwd_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, g, dx,
+                     M, P, ldx, ldg, lddx, eps);
+  MC_CHECK_LAUNCH("maeclip_l2_normalize_bwd");
   return 0;
 }
 

@@ -27,7 +27,9 @@
 //   total order, so the result does not depend on the slice count.
 // first_hit (labels given): smallest t with g_label[idx[q][t]] == q_label[q],
 //   else k; written by whichever kernel writes the final list.
-#include "common.h"
+// The dot tile and its MFMA k mapping are simtile.h's, shared with
+// clip_loss.hip and contrastive.hip.
+#include "simtile.h"
 #include "../../include/maeclip.h"
 
 namespace {
@@ -55,8 +57,6 @@ struct SimK {
   const int64_t* gl;
   int32_t* fh;
 };
-
-__device__ __forceinline__ v4f mma4(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // is (v, i) ranked before (bv, bi)?  value descending, index ascending
 __device__ __forceinline__ bool before(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
@@ -167,22 +167,6 @@ __device__ __forceinline__ void list_insert(float* rv, int* ri, int k, float v, 
   }
 }
 
-// 16 x 16 scores of one gallery tile: D[j = 4 g + reg][i = lane & 15]; FULL: P = 16 NV
-template <int NV, bool FULL>
-__device__ __forceinline__ v4f score_tile(const float* rowp, const v4f (&qr)[NV], int nv) {
-  v4f c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int b = 0; b < NV; ++b)
-    if (FULL || b < nv) {
-      const v4f x = *(const v4f*)(rowp + 16 * b);
-      c0 = mma4(x[0], qr[b][0], c0);
-      c1 = mma4(x[1], qr[b][1], c1);
-      c0 = mma4(x[2], qr[b][2], c0);
-      c1 = mma4(x[3], qr[b][3], c1);
-    }
-  return c0 + c1;
-}
-
 // NV: 16-float k-groups held per lane (P <= 16 NV)
 template <int NV>
 __global__ void __launch_bounds__(NT) sim_topk_kernel(const SimK a) {
@@ -231,8 +215,10 @@ __global__ void __launch_bounds__(NT) sim_topk_kernel(const SimK a) {
     __syncthreads();
     if (jt + 1 < jt1) st.load(a, (int64_t)GT * (jt + 1), jend);
     if (!wave_on) continue;
+    // 16 x 16 scores of the tile: D[j = 4 g + reg][i = lane & 15]; P < 16 NV
+    // takes the k-groups below nv alone
     const float* rowp = Gt + il * RS + 4 * g;
-    const v4f d = nv == NV ? score_tile<NV, true>(rowp, qr, nv) : score_tile<NV, false>(rowp, qr, nv);
+    const v4f d = nv == NV ? dot_tile<NV>(rowp, qr) : dot_tile<NV>(rowp, qr, nv);
     const int64_t jb = (int64_t)GT * jt + 4 * g;
     float thv = tv[rowl];
     int thi = ti[rowl];

@@ -994,15 +994,56 @@ class ProjectionHeadFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------- CLIP loss
+def gather_pair(I, T, group):
+    """The data-parallel gather of both losses: contiguous (I, T, rows). With a
+    group of more than one rank the local [B, P] embeddings of every rank are
+    all-gathered in rank order (the global contrastive denominator, SURVEY
+    §8e) and rows = (rank * B, B) is the rank's own slice of the gathered
+    batch; otherwise the inputs as given and rows = None (all rows)."""
+    I, T = I.contiguous(), T.contiguous()
+    if group is not None:
+        from .distributed import all_gather_rows, world_rank, check_equal_rows
+        world, rank = world_rank(group)
+        if world > 1:
+            B = I.shape[0]
+            check_equal_rows(B, group, I.device)
+            return all_gather_rows(I, group), all_gather_rows(T, group), (rank * B, B)
+    return I, T, None
+
+
+def _scale_pair_grads(ctx, gl, params):
+    """Backward of both loss Functions: ctx.grads = (dI, dT, one scalar gradient
+    per parameter of params that is not None, in that order) scaled by the
+    device grad_output gl. Returns (dI, dT, one gradient or None per entry of
+    params), the scalar gradients in their parameters' arena slots."""
+    dI, dT, *scalars = ctx.grads
+    ctx.grads = None
+    s = gl.reshape(1).contiguous()
+    out = [None] * len(params)
+    live = [k for k, p in enumerate(params) if p is not None]
+    if not live:
+        # scaled in place by the device grad_output: one launch, no host sync
+        K.scale_by_scalar(s, 1.0, dI, dT, dI, dT)
+        return (dI, dT, *out)
+    # dI, dT are the halves of one buffer: scaled in place as one tensor, and
+    # the first scalar gradient into its parameter's slot in the same launch;
+    # a second one in a launch of its own
+    both = dI._base.view(-1)
+    k = live[0]
+    _, out[k] = K.scale_by_scalar(s, 1.0, both, scalars[0], both, gout(ctx.arena, params[k]))
+    for k, d in zip(live[1:], scalars[1:]):
+        out[k], _ = K.scale_by_scalar(s, 1.0, d, None, gout(ctx.arena, params[k]))
+    return (dI, dT, *out)
+
+
 class ClipLossFn(torch.autograd.Function):
     """CLIP.py:34-43 on the fused fp32 kernel (the gradients come out of the
     same call; the backward only scales them by grad_output).
 
-    group (data parallel, world > 1): the local [B, P] embeddings of every rank
-    are all-gathered in rank order (the global contrastive denominator, SURVEY
-    §8e), every rank evaluates the loss of the gathered batch and asks the
-    kernel for the gradient of its own B rows only -- so a SUM all-reduce of
-    the parameter gradients is the exact global-batch gradient."""
+    group (data parallel, world > 1): gather_pair; every rank evaluates the
+    loss of the gathered batch and asks the kernel for the gradient of its own
+    B rows only -- so a SUM all-reduce of the parameter gradients is the exact
+    global-batch gradient."""
 
     @staticmethod
     def forward(ctx, I, T, temperature, group=None, log_temperature=None):
@@ -1011,45 +1052,17 @@ class ClipLossFn(torch.autograd.Function):
         requires grad, d loss / d theta comes out of the same call. Under data
         parallelism it is the sum over the rank's own rows, so the SUM
         all-reduce of the parameter gradients needs no rescale."""
-        I = I.contiguous()
-        T = T.contiguous()
-        rows = None
-        if group is not None:
-            from .distributed import all_gather_rows, world_rank, check_equal_rows
-            world, rank = world_rank(group)
-            if world > 1:
-                B = I.shape[0]
-                check_equal_rows(B, group, I.device)
-                I = all_gather_rows(I, group)
-                T = all_gather_rows(T, group)
-                rows = (rank * B, B)
+        I, T, rows = gather_pair(I, T, group)
         lt = None if log_temperature is None else log_temperature.detach()
         ctx.theta = log_temperature if lt is not None and ctx.needs_input_grad[4] else None
-        if ctx.theta is not None:
-            loss, dI, dT, dth = K.clip_loss(I, T, temperature, want_grad=True, grad_rows=rows, log_temperature=lt,
-                                            want_dtemp=True)
-            ctx.grads = (dI, dT, dth)
-        else:
-            loss, dI, dT = K.clip_loss(I, T, temperature, want_grad=True, grad_rows=rows, log_temperature=lt)
-            ctx.grads = (dI, dT)
+        loss, *ctx.grads = K.clip_loss(I, T, temperature, want_grad=True, grad_rows=rows, log_temperature=lt,
+                                       want_dtemp=ctx.theta is not None)
         ctx.arena = _arena()
         return loss
 
     @staticmethod
     def backward(ctx, gl):
-        grads = ctx.grads
-        ctx.grads = None
-        s = gl.reshape(1).contiguous()
-        if ctx.theta is None:
-            dI, dT = grads
-            # scaled in place by the device grad_output: one launch, no host sync
-            K.scale_by_scalar(s, 1.0, dI, dT, dI, dT)
-            return dI, dT, None, None, None
-        # dI, dT are the halves of one buffer: scaled in place as one tensor, and
-        # d theta into the parameter's gradient slot, in the same launch
-        dI, dT, dth = grads
-        both = dI._base.view(-1)
-        _, dth = K.scale_by_scalar(s, 1.0, both, dth, both, gout(ctx.arena, ctx.theta))
+        dI, dT, dth = _scale_pair_grads(ctx, gl, (ctx.theta,))
         return dI, dT, None, None, dth
 
 
@@ -1062,49 +1075,20 @@ class ContrastiveLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, I, T, kind, temperature, group=None, log_temperature=None, logit_bias=None):
-        I = I.contiguous()
-        T = T.contiguous()
-        rows = None
-        if group is not None:
-            from .distributed import all_gather_rows, world_rank, check_equal_rows
-            world, rank = world_rank(group)
-            if world > 1:
-                B = I.shape[0]
-                check_equal_rows(B, group, I.device)
-                I = all_gather_rows(I, group)
-                T = all_gather_rows(T, group)
-                rows = (rank * B, B)
+        I, T, rows = gather_pair(I, T, group)
         lt = None if log_temperature is None else log_temperature.detach()
         lb = None if logit_bias is None else logit_bias.detach()
         ctx.theta = log_temperature if lt is not None and ctx.needs_input_grad[5] else None
         ctx.bias = logit_bias if lb is not None and ctx.needs_input_grad[6] else None
-        out = K.contrastive_loss(I, T, kind, temperature, want_grad=True, grad_rows=rows, log_temperature=lt,
-                                 logit_bias=lb, want_dtemp=ctx.theta is not None, want_dbias=ctx.bias is not None)
-        ctx.grads = out[1:]
+        loss, *ctx.grads = K.contrastive_loss(I, T, kind, temperature, want_grad=True, grad_rows=rows,
+                                              log_temperature=lt, logit_bias=lb, want_dtemp=ctx.theta is not None,
+                                              want_dbias=ctx.bias is not None)
         ctx.arena = _arena()
-        return out[0]
+        return loss
 
     @staticmethod
     def backward(ctx, gl):
-        grads = list(ctx.grads)
-        ctx.grads = None
-        s = gl.reshape(1).contiguous()
-        dI, dT = grads[0], grads[1]
-        if ctx.theta is None and ctx.bias is None:
-            # scaled in place by the device grad_output: one launch, no host sync
-            K.scale_by_scalar(s, 1.0, dI, dT, dI, dT)
-            return dI, dT, None, None, None, None, None
-        # dI, dT are the halves of one buffer: scaled in place as one tensor, and
-        # the first scalar gradient into its parameter's slot in the same launch
-        both = dI._base.view(-1)
-        scalars = grads[2:]
-        dth = db = None
-        if ctx.theta is not None:
-            _, dth = K.scale_by_scalar(s, 1.0, both, scalars.pop(0), both, gout(ctx.arena, ctx.theta))
-            if ctx.bias is not None:
-                db, _ = K.scale_by_scalar(s, 1.0, scalars.pop(0), None, gout(ctx.arena, ctx.bias))
-        else:
-            _, db = K.scale_by_scalar(s, 1.0, both, scalars.pop(0), both, gout(ctx.arena, ctx.bias))
+        dI, dT, dth, db = _scale_pair_grads(ctx, gl, (ctx.theta, ctx.bias))
         return dI, dT, None, None, None, dth, db
 
 

@@ -764,6 +764,45 @@ def mae_loss_bwd(pred, img, mask, p, norm_pix, grad_out, mask_count, loss_scale=
 
 
 # --------------------------------------------------------------- CLIP loss
+def _pair_loss(who, Args, ws_bytes_of, I, T, want_grad, grad_rows, row_loss, scalars, wants, **fields):
+    """What clip_loss and contrastive_loss share (who: the public name, and
+    "maeclip_" + who the entry point). scalars: args field -> optional device
+    f32 [1] parameter; wants: args field of a scalar gradient -> asked for, in
+    result order; fields: the other fields of Args. ws_bytes_of(N, P, gradient
+    rows) sizes the workspace. Returns (loss, dI, dT[, rl][, one f32 [1] per
+    gradient asked for]); with any of those, dI and dT are the two halves of
+    one buffer (dI._base), so one launch can scale both."""
+    _dev(I, T)
+    N, P = I.shape
+    r0, nr = (0, N) if grad_rows is None else grad_rows
+    if not (0 <= r0 and nr >= 1 and r0 + nr <= N):
+        raise ValueError(f"{who}: gradient rows {grad_rows} out of range for N={N}")
+    for name, t in scalars.items():
+        if t is not None:
+            _dev(t)
+            if t.dtype != torch.float32 or t.numel() != 1:
+                raise ValueError(f"{who}: {name} must be one f32 element")
+    if wants["d_log_temperature"] and (scalars["log_temperature"] is None or not want_grad):
+        raise ValueError(f"{who}: want_dtemp needs log_temperature and want_grad")
+    f32 = dict(device=I.device, dtype=torch.float32)
+    ws_bytes = int(ws_bytes_of(N, P, nr if want_grad else 0))
+    ws = torch.empty((max(ws_bytes // 4, 4),), **f32)
+    loss = torch.empty((), **f32)
+    if any(wants.values()):
+        dI, dT = torch.empty((2, nr, P), **f32).unbind(0)
+    else:
+        dI = torch.empty((nr, P), **f32) if want_grad else None
+        dT = torch.empty((nr, P), **f32) if want_grad else None
+    rl = torch.empty((N,), **f32) if row_loss else None
+    ds = {name: torch.empty((1,), **f32) if w else None for name, w in wants.items()}
+    a = Args(I=I.data_ptr(), T=T.data_ptr(), ld_I=I.stride(0), ld_T=T.stride(0), N=N, P=P, loss=loss.data_ptr(),
+             row_loss_out=_ptr(rl), dI=_ptr(dI), dT=_ptr(dT), ld_dI=P, ld_dT=P, grad_row0=r0, grad_rows=nr,
+             workspace=ws.data_ptr(), ws_bytes=ws_bytes, **{name: _ptr(t) for name, t in scalars.items()},
+             **{name: _ptr(d) for name, d in ds.items()}, **fields)
+    _call("maeclip_" + who, C.byref(a), _stream())
+    return (loss, dI, dT) + ((rl,) if row_loss else ()) + tuple(d for d in ds.values() if d is not None)
+
+
 def clip_loss(I, T, temperature, want_grad=True, grad_rows=None, row_loss=False, log_temperature=None,
               want_dtemp=False):
     """Fused soft-target CLIP loss (CLIP.py:34-43). grad_rows = (row0, count):
@@ -775,34 +814,9 @@ def clip_loss(I, T, temperature, want_grad=True, grad_rows=None, row_loss=False,
     log_temperature and want_grad): d loss / d theta of the gradient rows as a
     device f32 [1] tensor, appended to the result; dI and dT are then the two
     halves of one buffer (dI._base), so one launch can scale both."""
-    _dev(I, T)
-    N, P = I.shape
-    r0, nr = (0, N) if grad_rows is None else grad_rows
-    if not (0 <= r0 and nr >= 1 and r0 + nr <= N):
-        raise ValueError(f"clip_loss: gradient rows {grad_rows} out of range for N={N}")
-    if log_temperature is not None:
-        _dev(log_temperature)
-        if log_temperature.dtype != torch.float32 or log_temperature.numel() != 1:
-            raise ValueError("clip_loss: log_temperature must be one f32 element")
-    if want_dtemp and (log_temperature is None or not want_grad):
-        raise ValueError("clip_loss: want_dtemp needs log_temperature and want_grad")
-    ws_bytes = int(L.lib().maeclip_clip_loss_workspace(N, P, nr if want_grad else 0))
-    ws = torch.empty((ws_bytes // 4,), device=I.device, dtype=torch.float32)
-    loss = torch.empty((), device=I.device, dtype=torch.float32)
-    if want_dtemp:
-        dI, dT = torch.empty((2, nr, P), device=I.device, dtype=torch.float32).unbind(0)
-    else:
-        dI = torch.empty((nr, P), device=I.device, dtype=torch.float32) if want_grad else None
-        dT = torch.empty((nr, P), device=I.device, dtype=torch.float32) if want_grad else None
-    rl = torch.empty((N,), device=I.device, dtype=torch.float32) if row_loss else None
-    dth = torch.empty((1,), device=I.device, dtype=torch.float32) if want_dtemp else None
-    a = L.ClipArgs(I=I.data_ptr(), T=T.data_ptr(), ld_I=I.stride(0), ld_T=T.stride(0), N=N, P=P,
-                   temperature=float(temperature), loss=loss.data_ptr(), row_loss_out=_ptr(rl), dI=_ptr(dI),
-                   dT=_ptr(dT), ld_dI=P, ld_dT=P, grad_row0=r0, grad_rows=nr, workspace=ws.data_ptr(),
-                   ws_bytes=ws_bytes, log_temperature=_ptr(log_temperature), d_log_temperature=_ptr(dth))
-    _call("maeclip_clip_loss", C.byref(a), _stream())
-    out = (loss, dI, dT) + ((rl,) if row_loss else ()) + ((dth,) if want_dtemp else ())
-    return out
+    return _pair_loss("clip_loss", L.ClipArgs, lambda N, P, g: L.lib().maeclip_clip_loss_workspace(N, P, g), I, T,
+                      want_grad, grad_rows, row_loss, {"log_temperature": log_temperature},
+                      {"d_log_temperature": want_dtemp}, temperature=float(temperature))
 
 
 INFONCE, SIGLIP = 0, 1
@@ -822,39 +836,15 @@ def contrastive_loss(I, T, kind, temperature, want_grad=True, grad_rows=None, ro
     kind = CONTRASTIVE_KINDS.get(kind, kind)
     if kind not in (INFONCE, SIGLIP):
         raise ValueError(f"contrastive_loss: kind must be 'infonce' or 'siglip', got {kind!r}")
-    N, P = I.shape
-    r0, nr = (0, N) if grad_rows is None else grad_rows
-    if not (0 <= r0 and nr >= 1 and r0 + nr <= N):
-        raise ValueError(f"contrastive_loss: gradient rows {grad_rows} out of range for N={N}")
-    for name, t in (("log_temperature", log_temperature), ("logit_bias", logit_bias)):
-        if t is not None:
-            _dev(t)
-            if t.dtype != torch.float32 or t.numel() != 1:
-                raise ValueError(f"contrastive_loss: {name} must be one f32 element")
     if logit_bias is not None and kind != SIGLIP:
         raise ValueError("contrastive_loss: logit_bias is SigLIP's only")
-    if want_dtemp and (log_temperature is None or not want_grad):
-        raise ValueError("contrastive_loss: want_dtemp needs log_temperature and want_grad")
     if want_dbias and (kind != SIGLIP or not want_grad):
         raise ValueError("contrastive_loss: want_dbias needs SigLIP and want_grad")
-    ws_bytes = int(L.lib().maeclip_contrastive_workspace(N, P, nr if want_grad else 0, kind))
-    ws = torch.empty((max(ws_bytes // 4, 4),), device=I.device, dtype=torch.float32)
-    loss = torch.empty((), device=I.device, dtype=torch.float32)
-    if want_dtemp or want_dbias:
-        dI, dT = torch.empty((2, nr, P), device=I.device, dtype=torch.float32).unbind(0)
-    else:
-        dI = torch.empty((nr, P), device=I.device, dtype=torch.float32) if want_grad else None
-        dT = torch.empty((nr, P), device=I.device, dtype=torch.float32) if want_grad else None
-    rl = torch.empty((N,), device=I.device, dtype=torch.float32) if row_loss else None
-    dth = torch.empty((1,), device=I.device, dtype=torch.float32) if want_dtemp else None
-    db = torch.empty((1,), device=I.device, dtype=torch.float32) if want_dbias else None
-    a = L.ContrastiveArgs(I=I.data_ptr(), T=T.data_ptr(), ld_I=I.stride(0), ld_T=T.stride(0), N=N, P=P, kind=kind,
-                          temperature=float(temperature), log_temperature=_ptr(log_temperature),
-                          logit_bias=_ptr(logit_bias), loss=loss.data_ptr(), row_loss_out=_ptr(rl), dI=_ptr(dI),
-                          dT=_ptr(dT), ld_dI=P, ld_dT=P, grad_row0=r0, grad_rows=nr, d_log_temperature=_ptr(dth),
-                          d_logit_bias=_ptr(db), workspace=ws.data_ptr(), ws_bytes=ws_bytes)
-    _call("maeclip_contrastive_loss", C.byref(a), _stream())
-    return (loss, dI, dT) + ((rl,) if row_loss else ()) + ((dth,) if want_dtemp else ()) + ((db,) if want_dbias else ())
+    return _pair_loss("contrastive_loss", L.ContrastiveArgs,
+                      lambda N, P, g: L.lib().maeclip_contrastive_workspace(N, P, g, kind), I, T, want_grad, grad_rows,
+                      row_loss, {"log_temperature": log_temperature, "logit_bias": logit_bias},
+                      {"d_log_temperature": want_dtemp, "d_logit_bias": want_dbias}, kind=kind,
+                      temperature=float(temperature))
 
 
 def _rows_f32(x, what):
