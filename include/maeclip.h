@@ -546,6 +546,73 @@ typedef struct {
 } maeclip_preprocess_args;
 int32_t maeclip_image_preprocess_u8(const maeclip_preprocess_args* args, void* stream);
 
+/* Training augmentation on the device: A.RandomResizedCrop(S, S, scale, ratio,
+ * INTER_LINEAR) -> A.HorizontalFlip(p) -> (A.Normalize + permute), drawn from
+ * the device step so that a replayed graph sees new pixels every step.
+ *
+ * maeclip_crop_params draws one box per sample: boxes int32 [B][5] = (x0, y0,
+ * w, h, flip). Source sizes (H, W) of sample b: images[b].H / .W when `images`
+ * is set, else sizes[2b], sizes[2b + 1] (clamped to [1, H] x [1, W]) when
+ * `sizes` is set, else H x W for every sample. All arithmetic is double, in
+ * exactly this order (input.hip mc_crop_draw; no fused multiply-add):
+ *   step_seed = seed + (*step_ptr) * MAECLIP_STEP_MULT      (seed if NULL)
+ *   u(k, f)   = (mc_hash4(step_seed, sample_offset + b, k, f) >> 8) * 2^-24
+ *   lr0 = log(ratio[0]), lr1 = log(ratio[1])
+ *   for attempt k = 0 .. 9:
+ *     area = (H * W) * (scale[0] + u(k, 0) * (scale[1] - scale[0]))
+ *     ar   = exp(lr0 + u(k, 1) * (lr1 - lr0))
+ *     w = rint(sqrt(area * ar)), h = rint(sqrt(area / ar))   (ties to even)
+ *     if 0 < w <= W and 0 < h <= H:
+ *       y0 = floor(u(k, 2) * (H - h + 1)), x0 = floor(u(k, 3) * (W - w + 1)); stop
+ *   after ten failures (get_params' centre crop), with in = W / H:
+ *     in < ratio[0]: w = W, h = clamp(rint(W / ratio[0]), 1, H)
+ *     in > ratio[1]: h = H, w = clamp(rint(H * ratio[1]), 1, W)
+ *     else         : w = W, h = H
+ *     y0 = (H - h) / 2, x0 = (W - w) / 2                     (integer division)
+ *   flip = u(10, 4) < flip_p
+ * maeclip_crop_params_host evaluates the same function on the CPU: every
+ * pointer (images, sizes, step_ptr, boxes) is a HOST pointer, only H / W of a
+ * descriptor are read, and nothing touches a device. exp / log may differ in
+ * the last bit between the two, which can only matter where sqrt(...) lies
+ * within ~1e-13 of a half-integer. */
+typedef struct {
+  const maeclip_image_src* images; /* optional: per-sample sizes from descriptors */
+  const int32_t* sizes;            /* optional int32 [B][2] = (h, w); needs H, W > 0 */
+  int32_t H, W;                    /* size of every sample / of a padded slot */
+  int32_t* boxes;
+  int32_t B;
+  float scale[2], ratio[2], flip_p;
+  uint64_t seed, sample_offset;
+  const int64_t* step_ptr;
+} maeclip_crop_params_args;
+int32_t maeclip_crop_params(const maeclip_crop_params_args* args, void* stream);
+int32_t maeclip_crop_params_host(const maeclip_crop_params_args* args);
+
+/* crop -> resize -> flip -> store for a batch, boxes read from device memory
+ * (maeclip_crop_params' or the caller's). Source: EITHER `images` (device
+ * descriptor array, any sizes, row-strided) OR `batch`, a dense padded uint8
+ * [B][Hmax][Wmax][3] with optional device `sizes` int32 [B][2] = valid (h, w)
+ * of each slot (clamped to the slot). Every box is clamped into its image
+ * (x0 in [0, W-1], w in [1, W-x0], likewise y), then the w x h crop is resized
+ * to S x S exactly as maeclip_image_preprocess_u8 resizes a whole image
+ * (copy at S x S, INTER_AREA at 2S x 2S, fixed-point INTER_LINEAR otherwise)
+ * and mirrored when flip != 0: out[.., x] = resized[.., S-1-x]. Destinations
+ * (at least one): dst_f32 fp32 [B][3][S][S], normalised as
+ * maeclip_image_normalize_u8 does; dst_u8 uint8 [B][S][S][3]. */
+typedef struct {
+  const maeclip_image_src* images;
+  const uint8_t* batch;
+  const int32_t* sizes;
+  int32_t Hmax, Wmax;
+  const int32_t* boxes;
+  float* dst_f32;
+  uint8_t* dst_u8;
+  int64_t B, S;
+  float mean[3], std[3];
+  float max_pixel;
+} maeclip_augment_args;
+int32_t maeclip_image_augment_u8(const maeclip_augment_args* args, void* stream);
+
 /* Retrieval (inference.py:40-45). l2_normalize replaces F.normalize(x, p=2,
  * dim=-1): y = x / max(||x||_2, eps), fp32 [M][P] rows (strides ldx / ldy).
  * topk_rows replaces torch.topk(dot_similarity, k) row-wise: s fp32 [Q][N]

@@ -152,6 +152,18 @@ class ImageU8Args(C.Structure):
                 ("mean", c_f32 * 3), ("std", c_f32 * 3), ("max_pixel", c_f32)]
 
 
+class CropParamsArgs(C.Structure):
+    _fields_ = [("images", c_vp), ("sizes", c_vp), ("H", c_i32), ("W", c_i32), ("boxes", c_vp), ("B", c_i32),
+                ("scale", c_f32 * 2), ("ratio", c_f32 * 2), ("flip_p", c_f32),
+                ("seed", c_u64), ("sample_offset", c_u64), ("step_ptr", c_vp)]
+
+
+class AugmentArgs(C.Structure):
+    _fields_ = [("images", c_vp), ("batch", c_vp), ("sizes", c_vp), ("Hmax", c_i32), ("Wmax", c_i32),
+                ("boxes", c_vp), ("dst_f32", c_vp), ("dst_u8", c_vp), ("B", c_i64), ("S", c_i64),
+                ("mean", c_f32 * 3), ("std", c_f32 * 3), ("max_pixel", c_f32)]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "maeclip_abi_version": (c_i32, []),
@@ -176,6 +188,9 @@ _SIGS = {
     "maeclip_wgrad_grouped": (c_i32, [C.POINTER(WgradProblem), c_i32, c_i64, c_i32, c_f32, c_vp, c_i64, c_vp]),
     "maeclip_image_normalize_u8": (c_i32, [C.POINTER(ImageU8Args), c_vp]),
     "maeclip_image_preprocess_u8": (c_i32, [C.POINTER(PreprocessArgs), c_vp]),
+    "maeclip_crop_params": (c_i32, [C.POINTER(CropParamsArgs), c_vp]),
+    "maeclip_crop_params_host": (c_i32, [C.POINTER(CropParamsArgs)]),
+    "maeclip_image_augment_u8": (c_i32, [C.POINTER(AugmentArgs), c_vp]),
     "maeclip_l2_normalize": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_f32, c_vp]),
     "maeclip_topk_rows": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "maeclip_sim_topk_splits": (c_i32, [c_i64, c_i64, c_i64, c_i32, c_i32]),

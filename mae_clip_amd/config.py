@@ -86,6 +86,13 @@ fp8_attn_q8 = tuple(c == "1" for c in __import__("os").environ.get("MAECLIP_FP8_
 fp8_decoder = __import__("os").environ.get("MAECLIP_FP8_DECODER", "1") == "1"
 mask_seed = 2
 dropout_seed = 1234
+# ---- training augmentation on the device (data.TrainAugment / data.train_augment_from_config): off by default,
+# the reference's only transform is Resize + Normalize (dataset.py:44-58). The defaults are MAE's / torchvision's.
+augment = False
+augment_scale = (0.08, 1.0)        # RandomResizedCrop: crop area as a share of the image
+augment_ratio = (3 / 4, 4 / 3)     # RandomResizedCrop: crop aspect ratio w / h, log-uniform
+augment_flip_p = 0.5               # HorizontalFlip probability
+augment_seed = 3
 # ---- scheduling
 side_stream = True         # frozen text tower || image encoder; weight-gradient GEMMs || the dgrad chain
 # data parallel: encoder blocks per autograd Function, in forward order (the

@@ -348,7 +348,7 @@ __host__ __device__ __forceinline__ uint64_t mc_mix64(uint64_t z) {
   return z ^ (z >> 31);
 }
 // seed of a dropout / noise draw at the current device step (MAECLIP_STEP_MULT, maeclip.h)
-__device__ __forceinline__ uint64_t mc_step_seed(uint64_t seed, const int64_t* step_ptr) {
+__host__ __device__ __forceinline__ uint64_t mc_step_seed(uint64_t seed, const int64_t* step_ptr) {
   return step_ptr ? seed + (uint64_t)(*step_ptr) * 0x9E3779B97F4A7C15ull : seed;
 }
 __host__ __device__ __forceinline__ uint32_t mc_hash4(uint64_t seed, uint64_t a, uint64_t b, uint64_t c) {

@@ -10,6 +10,12 @@ normalises and transposes them in HBM in one pass
 (maeclip_image_preprocess_u8 = Resize + Normalize + permute), producing
 exactly the tensor the model takes. normalize_u8 is the resize-free variant
 for batches already at the model's size.
+
+Training augmentation (nothing in the reference): TrainAugment =
+A.RandomResizedCrop + A.HorizontalFlip on the device, box and coin drawn from
+the model's device step counter (maeclip_crop_params), pixels by
+maeclip_image_augment_u8; crop_params / crop_params_host / augment_images are
+its parts.
 """
 from __future__ import annotations
 
@@ -49,18 +55,8 @@ def preprocess_images(images, size, mean=IMAGENET_MEAN, std=IMAGENET_STD, max_pi
     a list of uint8 HWC RGB images of any sizes (device tensors; row-strided
     views allowed) -> float32 [B, 3, size, size]: A.Resize(size, size) with
     cv2.INTER_LINEAR semantics, then A.Normalize."""
-    if not images:
-        raise ValueError("preprocess_images: empty image list")
-    dev = images[0].device
-    descs = (L.ImageSrc * len(images))()
-    for i, im in enumerate(images):
-        _dev(im)
-        if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or im.stride(2) != 1 or im.stride(1) != 3:
-            raise ValueError(f"preprocess_images: image {i} must be uint8 [H, W, 3] with packed pixels")
-        if im.device != dev:
-            raise ValueError("preprocess_images: images on different devices")
-        descs[i].src, descs[i].H, descs[i].W, descs[i].row_stride = im.data_ptr(), im.shape[0], im.shape[1], im.stride(0)
-    B = len(images)
+    descs = _descriptors(images, "preprocess_images")
+    dev, B = images[0].device, len(images)
     if out is None:
         out = torch.empty((B, 3, size, size), device=dev, dtype=torch.float32)
     elif out.shape != (B, 3, size, size) or out.dtype != torch.float32 or not out.is_contiguous():
@@ -72,9 +68,172 @@ def preprocess_images(images, size, mean=IMAGENET_MEAN, std=IMAGENET_STD, max_pi
     return out
 
 
-def to_device_batch(images_u8, input_ids, attention_mask, device, non_blocking=True):
+def _descriptors(images, who):
+    """maeclip_image_src array (host) of a list of uint8 [H, W, 3] device images."""
+    if not images:
+        raise ValueError(f"{who}: empty image list")
+    dev = images[0].device
+    descs = (L.ImageSrc * len(images))()
+    for i, im in enumerate(images):
+        _dev(im)
+        if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or im.stride(2) != 1 or im.stride(1) != 3:
+            raise ValueError(f"{who}: image {i} must be uint8 [H, W, 3] with packed pixels")
+        if im.device != dev:
+            raise ValueError(f"{who}: images on different devices")
+        descs[i].src, descs[i].H, descs[i].W, descs[i].row_stride = im.data_ptr(), im.shape[0], im.shape[1], im.stride(0)
+    return descs
+
+
+# ------------------------------------------------- RandomResizedCrop + flip
+def _source(src, sizes, who):
+    """The two source forms of the augmentation entry points: a list of uint8
+    [H, W, 3] device images (descriptor array, uploaded here) or one padded
+    uint8 [B, Hmax, Wmax, 3] device batch with optional int32 [B, 2] valid
+    (h, w) per slot. -> (B, device, struct fields, tensors to keep alive)."""
+    if isinstance(src, (list, tuple)):
+        if sizes is not None:
+            raise ValueError(f"{who}: sizes belongs to the padded-batch form; a list carries its own sizes")
+        descs = _descriptors(src, who)
+        d = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(src[0].device)
+        return len(src), src[0].device, dict(images=d.data_ptr()), (d,)
+    _dev(src, sizes)
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[-1] != 3 or not src.is_contiguous():
+        raise ValueError(f"{who}: expected a list of images or a dense uint8 [B, Hmax, Wmax, 3] batch")
+    B, Hm, Wm, _ = src.shape
+    if sizes is not None and (sizes.dtype != torch.int32 or sizes.shape != (B, 2) or not sizes.is_contiguous()
+                              or sizes.device != src.device):
+        raise ValueError(f"{who}: sizes must be a dense int32 [B, 2] of (h, w) on the batch's device")
+    return B, src.device, dict(batch=src.data_ptr(), sizes=None if sizes is None else sizes.data_ptr(),
+                               Hmax=Hm, Wmax=Wm), ()
+
+
+def _boxes_out(out, B, dev, who):
+    if out is None:
+        return torch.empty((B, 5), device=dev, dtype=torch.int32)
+    if out.shape != (B, 5) or out.dtype != torch.int32 or not out.is_contiguous():
+        raise ValueError(f"{who}: boxes must be a dense int32 [B, 5]")
+    return out
+
+
+def crop_params(src, sizes=None, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), flip_p=0.5, seed=0, step_ptr=None,
+                sample_offset=0, out=None):
+    """A.RandomResizedCrop.get_params + the HorizontalFlip coin for every
+    sample of `src` (either source form of augment_images), drawn on the
+    device from (seed, *step_ptr, sample_offset + b): int32 [B, 5] =
+    (x0, y0, w, h, flip). step_ptr: device int64 step counter (None: step 0)."""
+    B, dev, fields, keep = _source(src, sizes, "crop_params")
+    _dev(step_ptr, out)
+    out = _boxes_out(out, B, dev, "crop_params")
+    if "batch" in fields:
+        fields = dict(sizes=fields["sizes"], H=fields["Hmax"], W=fields["Wmax"])
+    a = L.CropParamsArgs(boxes=out.data_ptr(), B=B, scale=(C.c_float * 2)(*scale), ratio=(C.c_float * 2)(*ratio),
+                         flip_p=flip_p, seed=int(seed), sample_offset=int(sample_offset),
+                         step_ptr=None if step_ptr is None else step_ptr.data_ptr(), **fields)
+    _call("maeclip_crop_params", C.byref(a), _stream())
+    return out
+
+
+def crop_params_host(sizes, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), flip_p=0.5, seed=0, step=0, sample_offset=0):
+    """The boxes crop_params draws at device step `step`, evaluated on the CPU
+    by the same function (no device needed): for logging, or to crop the box
+    annotations of step s. sizes: CPU int32 [B, 2] of (h, w). -> CPU int32 [B, 5]."""
+    sizes = torch.as_tensor(sizes, dtype=torch.int32).contiguous()
+    if sizes.is_cuda or sizes.dim() != 2 or sizes.shape[1] != 2:
+        raise ValueError("crop_params_host: sizes must be a CPU int32 [B, 2] of (h, w)")
+    B = sizes.shape[0]
+    out = torch.empty((B, 5), dtype=torch.int32)
+    step_v = C.c_int64(int(step))
+    lim = 2 ** 31 - 1
+    a = L.CropParamsArgs(sizes=sizes.data_ptr(), H=lim, W=lim, boxes=out.data_ptr(), B=B,
+                         scale=(C.c_float * 2)(*scale), ratio=(C.c_float * 2)(*ratio), flip_p=flip_p, seed=int(seed),
+                         sample_offset=int(sample_offset), step_ptr=C.addressof(step_v))
+    _call("maeclip_crop_params_host", C.byref(a))
+    return out
+
+
+def augment_images(src, boxes, size, out_dtype=torch.uint8, sizes=None, out=None, mean=IMAGENET_MEAN,
+                   std=IMAGENET_STD, max_pixel_value=255.0):
+    """crop -> cv2.resize(INTER_LINEAR) to size x size -> horizontal flip of
+    every sample by its row of `boxes` (device int32 [B, 5] = x0, y0, w, h,
+    flip; crop_params' or the caller's own, clamped into the image).
+    src: a list of uint8 [H, W, 3] device images of any sizes (row-strided
+    views allowed), or a padded uint8 [B, Hmax, Wmax, 3] batch with optional
+    `sizes` int32 [B, 2] = valid (h, w) per slot. out_dtype: torch.uint8 ->
+    [B, size, size, 3] pixels the model consumes as they are; torch.float32 ->
+    A.Normalize'd [B, 3, size, size] (the floats of normalize_u8)."""
+    B, dev, fields, keep = _source(src, sizes, "augment_images")
+    _dev(boxes, out)
+    if boxes is None:
+        raise ValueError("augment_images: boxes is required (crop_params draws them)")
+    boxes = _boxes_out(boxes, B, dev, "augment_images")
+    if out_dtype not in (torch.uint8, torch.float32):
+        raise ValueError("augment_images: out_dtype must be torch.uint8 or torch.float32")
+    shape = (B, size, size, 3) if out_dtype == torch.uint8 else (B, 3, size, size)
+    if out is None:
+        out = torch.empty(shape, device=dev, dtype=out_dtype)
+    elif out.shape != shape or out.dtype != out_dtype or not out.is_contiguous():
+        raise ValueError(f"augment_images: out must be a dense {out_dtype} {list(shape)}")
+    dst = dict(dst_u8=out.data_ptr()) if out_dtype == torch.uint8 else dict(dst_f32=out.data_ptr())
+    a = L.AugmentArgs(boxes=boxes.data_ptr(), B=B, S=size, mean=(C.c_float * 3)(*mean), std=(C.c_float * 3)(*std),
+                      max_pixel=max_pixel_value, **fields, **dst)
+    _call("maeclip_image_augment_u8", C.byref(a), _stream())
+    return out
+
+
+class TrainAugment:
+    """MAE's / CLIP's training augmentation on the device:
+    A.RandomResizedCrop(size, size, scale, ratio) -> A.HorizontalFlip(flip_p)
+    (-> A.Normalize + permute for out_dtype=torch.float32), with box and coin
+    drawn on the device from the step counter, so it can run inside a captured
+    step (graph.CapturedStep(transform=...)) and still change every replay.
+
+    __call__(batch, step_ptr, sample_offset=0) returns a new dict whose
+    "image" is the augmented batch; batch["image"] is either source form of
+    augment_images, an "image_sizes" entry gives the padded form's valid sizes
+    and is dropped, every other key passes through. Box and output buffers
+    are allocated once per batch size and reused: stable storage for capture
+    (`boxes` / `out` hold the last call's)."""
+
+    def __init__(self, size, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), flip_p=0.5, seed=None, out_dtype=torch.uint8):
+        from . import config as CFG
+        self.size, self.scale, self.ratio, self.flip_p = int(size), tuple(scale), tuple(ratio), float(flip_p)
+        self.seed = int(CFG.augment_seed if seed is None else seed)
+        self.out_dtype = out_dtype
+        self._bufs = {}
+        self.boxes = self.out = None
+
+    def __call__(self, batch, step_ptr, sample_offset=0):
+        src, sizes = batch["image"], batch.get("image_sizes")
+        B = len(src)
+        dev = src[0].device
+        if (B, dev) not in self._bufs:
+            shape = (B, self.size, self.size, 3) if self.out_dtype == torch.uint8 else (B, 3, self.size, self.size)
+            self._bufs[B, dev] = (torch.empty((B, 5), device=dev, dtype=torch.int32),
+                                  torch.empty(shape, device=dev, dtype=self.out_dtype))
+        self.boxes, self.out = self._bufs[B, dev]
+        crop_params(src, sizes, self.scale, self.ratio, self.flip_p, self.seed, step_ptr, sample_offset, out=self.boxes)
+        augment_images(src, self.boxes, self.size, self.out_dtype, sizes, out=self.out)
+        out = {k: v for k, v in batch.items() if k not in ("image", "image_sizes")}
+        out["image"] = self.out
+        return out
+
+
+def train_augment_from_config():
+    """TrainAugment of the config.augment_* flags, or None when config.augment is off."""
+    from . import config as CFG
+    if not CFG.augment:
+        return None
+    return TrainAugment(CFG.size, CFG.augment_scale, CFG.augment_ratio, CFG.augment_flip_p, CFG.augment_seed)
+
+
+def to_device_batch(images_u8, input_ids, attention_mask, device, non_blocking=True, augment=None, step_ptr=None,
+                    sample_offset=0):
     """The dict main.train_epoch feeds the model (main.py:55), built from a
-    host uint8 HWC batch: upload uint8, normalise on the device."""
+    host uint8 HWC batch: upload uint8, normalise on the device. augment (a
+    TrainAugment): the uploaded pixels go through it instead, drawn at
+    *step_ptr (the model's step_counter)."""
     imgs = images_u8.to(device, non_blocking=non_blocking)
-    return {"image": normalize_u8(imgs), "input_ids": input_ids.to(device, non_blocking=non_blocking),
-            "attention_mask": attention_mask.to(device, non_blocking=non_blocking)}
+    batch = {"image": imgs if augment is not None else normalize_u8(imgs),
+             "input_ids": input_ids.to(device, non_blocking=non_blocking),
+             "attention_mask": attention_mask.to(device, non_blocking=non_blocking)}
+    return batch if augment is None else augment(batch, step_ptr, sample_offset)

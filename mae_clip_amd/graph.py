@@ -20,6 +20,13 @@ Usage (drop-in around the reference's train_epoch body):
     for batch in loader:
         loss = runner.step(batch)      # model(batch); loss.backward(); optimizer.step()
 
+CapturedStep(..., transform=data.TrainAugment(size)): the step becomes
+model(transform(batch, model.step_counter, sample_offset)), with the
+transform's launches on the step's stream right before the forward, captured
+with it. The static buffers hold the raw batch (for a graph: tensors of a
+fixed shape, e.g. a padded uint8 batch), and the transform draws from the
+step counter, so every replay crops anew. transform=None: nothing changes.
+
 Data parallel (CapturedStep(..., dp=DataParallel(model))): the step becomes
 model(batch); backward; dp.sync_gradients(); optimizer.step(), and the RCCL
 collectives (the embedding all-gather of the forward, the bucketed gradient
@@ -36,10 +43,11 @@ from . import kernels as K
 
 
 class CapturedStep:
-    def __init__(self, model, optimizer, enabled: bool = True, eager_steps: int = 1, dp=None):
+    def __init__(self, model, optimizer, enabled: bool = True, eager_steps: int = 1, dp=None, transform=None):
         self.model = model
         self.opt = optimizer
         self.dp = dp
+        self.transform = transform
         if dp is not None and torch.distributed.get_backend(dp.group) != "nccl":
             enabled = False
         self.enabled = enabled
@@ -133,9 +141,18 @@ class CapturedStep:
         ev.synchronize()
         return self._host.values(self._slot(c))[0]
 
+    def _transformed(self, batch):
+        """transform(batch, step_counter, sample_offset) on the step's stream, right
+        before the forward: it reads the counter value that forward will use (and
+        advance). sample_offset = rank * B under dp, like the MAE mask's."""
+        if self.transform is None:
+            return batch
+        rank = torch.distributed.get_rank(self.dp.group) if self.dp is not None else 0
+        return self.transform(batch, self.model.step_counter, rank * len(batch["image"]))
+
     def _eager(self, batch):
         self.opt.zero_grad(set_to_none=True)
-        loss = self.model(batch)
+        loss = self.model(self._transformed(batch))
         loss.backward()
         if self.dp is not None:
             self.dp.sync_gradients()
@@ -164,7 +181,7 @@ class CapturedStep:
             cap = torch.cuda.current_stream().cuda_stream
             K.alias_stream(cap, replay)
             try:
-                loss = self.model(self.static)
+                loss = self.model(self._transformed(self.static))
                 torch.autograd.backward(loss, grad_tensors=one.expand_as(loss) if loss.dim() else one)
                 if self.dp is not None:
                     self.dp.sync_gradients()
