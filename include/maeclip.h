@@ -813,6 +813,68 @@ int32_t maeclip_contrastive_loss(const maeclip_contrastive_args* args, void* str
 int32_t maeclip_l2_normalize_bwd(const float* x, const float* g, float* dx, int64_t M, int64_t P, int64_t ldx,
                                  int64_t ldg, int64_t lddx, float eps, void* stream);
 
+/* ------------------------------------------------- softmax cross-entropy
+ * torch.nn.functional.cross_entropy(reduction="mean") with label_smoothing over
+ * class logits [M, C], fp32, class-index or class-probability targets, fused
+ * and deterministic (fixed-order sums, no atomics; xent.hip). Per row i, row
+ * stride ld >= C; columns >= C are never read:
+ *   m = max_j x_j, lse = m + log sum_j exp(x_j - m), p_j = exp(x_j - lse)
+ *   hard (soft_targets = 0): t_j = (1 - eps) [j == labels[i]] + eps / C
+ *   soft (soft_targets = 1): t_j = (1 - eps) targets[i, j] + eps / C (row
+ *     stride ld_t >= C; the rows need not sum to 1)
+ *   r_i  = (sum_j t_j) lse - sum_j t_j x_j
+ *   loss = s sum_i r_i, s = loss_scale / M (loss_scale: 1, or 1 / world under
+ *     data parallelism)
+ *   dlogits_ij = g s ((sum_j t_j) p_ij - t_ij), g = *grad_output (NULL: 1)
+ *   rank_i = #{ j : x_j > x_y, or x_j == x_y and j < y }, y = labels[i]: top-k is
+ *     a hit iff rank < k, ties broken by index.
+ * Exactly one of labels and targets defines the loss: soft_targets = 0 takes
+ * labels and no targets, soft_targets = 1 takes targets; labels may then still
+ * be given, and only rank uses them. labels: int32 (label_dtype 0) or int64 (1).
+ * A hard label outside [0, C) is defined behaviour: the row's loss term is 0,
+ * its gradient row is zero and its rank is C. The divisor stays M -- unlike
+ * torch's ignore_index, which divides by the number of rows kept.
+ * 1 <= M < 2^31, 1 <= C < 2^31 (C = 1: loss 0, gradient 0), 0 <= eps < 1.
+ * Alignment: every float / int32 pointer 4 bytes, int64 labels 8 bytes, the
+ * workspace 16 bytes. The 16-byte loads and stores are used when the base of
+ * logits (and of targets, and in the backward of dlogits) is 16-byte aligned
+ * and its row stride is a multiple of 4; otherwise 4-byte accesses, same bits.
+ * maeclip_xent_fwd writes loss [1], lse [M], and when not NULL row_loss [M] (the
+ * terms s r_i, whose sum is the loss), lse_lo [M] and rank [M] (needs labels).
+ * lse_lo is the rounding error of lse = fl(m + log sum exp): the backward takes
+ * x - lse as (x - lse) - lse_lo, which keeps p exact to fp32 at |x| ~ 1e4 (NULL
+ * in the backward: 0). Launches: the row pass, then a one-workgroup reduce in
+ * double. workspace: >= maeclip_xent_workspace(M) bytes.
+ * maeclip_xent_bwd reads logits, lse (, lse_lo) and the targets and writes
+ * dlogits [M, ld_d], ld_d >= C, in one launch; columns C .. ld_d - 1 get exact
+ * zeros. dlogits == logits (with ld_d == ld) is allowed: every element is read
+ * by the thread that overwrites it, before it is overwritten. loss, row_loss,
+ * rank and the workspace are not used. */
+typedef struct {
+  const float* logits;
+  int64_t ld;
+  const void* labels;
+  int32_t label_dtype;
+  int32_t soft_targets;
+  const float* targets;
+  int64_t ld_t;
+  int64_t M, C;
+  float label_smoothing;
+  float loss_scale;
+  float* loss;
+  float* row_loss;
+  float* lse;
+  float* lse_lo;
+  int32_t* rank;
+  float* dlogits;
+  int64_t ld_d;
+  void* workspace;
+  size_t ws_bytes;
+} maeclip_xent_args;
+size_t maeclip_xent_workspace(int64_t M); /* host only */
+int32_t maeclip_xent_fwd(const maeclip_xent_args* args, void* stream);
+int32_t maeclip_xent_bwd(const maeclip_xent_args* args, const float* grad_output, void* stream);
+
 /* ------------------------------------------------------------ step state
  * Device-resident step counters (model RNG step, optimizer step t) so that a
  * whole training step can be captured once in a HIP graph and replayed. */

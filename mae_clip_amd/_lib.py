@@ -128,6 +128,14 @@ class ContrastiveArgs(C.Structure):
                 ("d_log_temperature", c_vp), ("d_logit_bias", c_vp), ("workspace", c_vp), ("ws_bytes", c_sz)]
 
 
+class XentArgs(C.Structure):
+    _fields_ = [("logits", c_vp), ("ld", c_i64), ("labels", c_vp), ("label_dtype", c_i32), ("soft_targets", c_i32),
+                ("targets", c_vp), ("ld_t", c_i64), ("M", c_i64), ("C", c_i64),
+                ("label_smoothing", c_f32), ("loss_scale", c_f32), ("loss", c_vp), ("row_loss", c_vp),
+                ("lse", c_vp), ("lse_lo", c_vp), ("rank", c_vp), ("dlogits", c_vp), ("ld_d", c_i64),
+                ("workspace", c_vp), ("ws_bytes", c_sz)]
+
+
 class WgradProblem(C.Structure):
     _fields_ = [("dy", c_vp), ("x", c_vp), ("dw", c_vp), ("N", c_i64), ("K", c_i64), ("ldy", c_i64), ("ldx", c_i64)]
 
@@ -235,6 +243,9 @@ _SIGS = {
     "maeclip_contrastive_workspace": (c_sz, [c_i64, c_i64, c_i64, c_i32]),
     "maeclip_contrastive_loss": (c_i32, [C.POINTER(ContrastiveArgs), c_vp]),
     "maeclip_l2_normalize_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32, c_vp]),
+    "maeclip_xent_workspace": (c_sz, [c_i64]),
+    "maeclip_xent_fwd": (c_i32, [C.POINTER(XentArgs), c_vp]),
+    "maeclip_xent_bwd": (c_i32, [C.POINTER(XentArgs), c_vp, c_vp]),
     "maeclip_counter_add": (c_i32, [c_vp, c_i64, c_vp]),
     "maeclip_counter_add_snap": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
     "maeclip_scalar_axpy": (c_i32, [c_vp, c_vp, C.c_float, c_vp, c_vp]),

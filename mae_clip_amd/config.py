@@ -93,6 +93,12 @@ augment_scale = (0.08, 1.0)        # RandomResizedCrop: crop area as a share of 
 augment_ratio = (3 / 4, 4 / 3)     # RandomResizedCrop: crop aspect ratio w / h, log-uniform
 augment_flip_p = 0.5               # HorizontalFlip probability
 augment_seed = 3
+# ---- supervised evaluation of a pretrained image encoder (classifier.ClassifierModel): linear probe and fine-tuning.
+# Read by ClassifierModel only; CLIPModel never looks at them.
+num_classes = 1000
+label_smoothing = 0.0              # F.cross_entropy's label_smoothing (MAE fine-tuning uses 0.1)
+classifier_trainable_encoder = False   # False: linear probe (frozen encoder, only the head trains); True: fine-tuning
+head_init_std = 0.02               # head.weight trunc-normal(std), head.bias zero (timm / MAE)
 # ---- scheduling
 side_stream = True         # frozen text tower || image encoder; weight-gradient GEMMs || the dgrad chain
 # data parallel: encoder blocks per autograd Function, in forward order (the

@@ -16,6 +16,8 @@ Reference ops replaced (file:line):
   TextStackFn         HF DistilBertModel, trainable (modules.py:34-51 with trainable=True)
   ProjectionHeadFn    modules.py:69-76 (always fp32)
   ClipLossFn          CLIP.py:34-43
+  ClassifierHeadFn    timm VisionTransformer.head (nn.Linear, always fp32)
+  SoftmaxXentFn       F.cross_entropy(label_smoothing; class-index or probability targets)
 """
 from __future__ import annotations
 
@@ -1122,3 +1124,77 @@ class CombineLossFn(torch.autograd.Function):
         g = gl.reshape(1).contiguous()
         gm, _ = K.scale_by_scalar(g, ctx.w, out_x=torch.empty((), device=g.device, dtype=torch.float32))
         return gl, gm, None
+
+
+# ------------------------------------------------- classifier head and loss
+@dataclass
+class HeadSpec:
+    C: int                        # classes; the GEMMs run over the padded width w_pad.shape[0]
+    w_pad: torch.Tensor           # [Cpad, D] fp32: the head weight, zero rows past C (the parameter when Cpad == C)
+    b_pad: torch.Tensor           # [Cpad] fp32 likewise
+
+
+class ClassifierHeadFn(torch.autograd.Function):
+    """logits = feat W^T + b in fp32 (timm's `head`), wired as ProjectionHeadFn.
+    The fp32 GEMM wants the class dimension a multiple of 4: it runs on the
+    zero-padded copies of spec ([Cpad, D], [Cpad]), the logits are [M, Cpad]
+    (columns >= C are zero weight rows: never part of the loss), and dW / db are
+    sliced back to the parameters' [C, D] / [C]."""
+
+    @staticmethod
+    def forward(ctx, feat, spec: HeadSpec, w, b):
+        feat = feat.contiguous()
+        ctx.save = (feat,)
+        ctx.spec = spec
+        ctx.params = (w, b)
+        ctx.arena = _arena()
+        return K.linear_fwd(feat, spec.w_pad, spec.b_pad)
+
+    @staticmethod
+    def backward(ctx, g):
+        (feat,) = ctx.save
+        spec = ctx.spec
+        w, b = ctx.params
+        ar = ctx.arena
+        g = g.contiguous()
+        C, Cpad = spec.C, spec.w_pad.shape[0]
+        dfeat = K.linear_dgrad(g, spec.w_pad, out_dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        cs = K.rows_colsum(g)
+        dW = gout(ar, w)
+        if Cpad != C:
+            dW.copy_(K.linear_wgrad(g, feat)[:C])
+            db = K.colsum_reduce(cs[:, :C].contiguous(), out=gout(ar, b))
+        else:
+            K.linear_wgrad(g, feat, out=dW)
+            db = K.colsum_reduce(cs, out=gout(ar, b))
+        return dfeat, None, dW, db
+
+
+@dataclass
+class XentSpec:
+    C: int
+    label_smoothing: float = 0.0
+    loss_scale: float = 1.0       # 1 / world under data parallelism
+
+
+class SoftmaxXentFn(torch.autograd.Function):
+    """loss = loss_scale * F.cross_entropy(logits[:, :C], labels or targets,
+    label_smoothing) on the fused fp32 kernel. The backward is one launch: the
+    kernel reads grad_output from the device (no host sync, no separate scale
+    pass) and zero-fills the pad columns the head's GEMMs run over."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, targets, spec: XentSpec):
+        out = K.xent_fwd(logits, labels if targets is None else None, targets, C=spec.C,
+                         label_smoothing=spec.label_smoothing, loss_scale=spec.loss_scale)
+        ctx.save = (logits, labels if targets is None else None, targets, out.lse, out.lse_lo)
+        ctx.spec = spec
+        return out.loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        logits, labels, targets, lse, lse_lo = ctx.save
+        spec = ctx.spec
+        d = K.xent_bwd(logits, lse, labels, targets, C=spec.C, label_smoothing=spec.label_smoothing,
+                       loss_scale=spec.loss_scale, grad_output=gl.reshape(1).contiguous(), lse_lo=lse_lo)
+        return d, None, None, None

@@ -7,6 +7,7 @@ CPU: tensors must live on a ROCm device.
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -873,6 +874,106 @@ def l2_normalize_bwd(x, g, eps=1e-12):
     _call("maeclip_l2_normalize_bwd", x.data_ptr(), g.data_ptr(), dx.data_ptr(), x.shape[0], x.shape[1], x.stride(0),
           g.stride(0), dx.stride(0), float(eps), _stream())
     return dx
+
+
+# ------------------------------------------------- softmax cross-entropy
+_byref = C.byref   # (C names the class count below, as in the header)
+XENT_WAVE_COLS = 256    # xent.hip: rows up to here take one wave each, longer ones a workgroup
+XENT_REG_COLS = 8192    # xent.hip: the forward holds rows up to here in registers, longer ones are streamed
+
+
+class XentOut(NamedTuple):
+    """xent_fwd's result: loss (0-d), lse and lse_lo ([M]: lse rounded to fp32 and
+    that rounding's error, both for xent_bwd), rank (int32 [M] or None) and
+    row_loss ([M] or None: the per-row terms, their sum is the loss)."""
+    loss: torch.Tensor
+    lse: torch.Tensor
+    lse_lo: torch.Tensor
+    rank: Optional[torch.Tensor]
+    row_loss: Optional[torch.Tensor]
+
+
+def _xent_args(who, logits, labels, targets, C, label_smoothing, loss_scale):
+    """The input half of XentArgs, checked: logits fp32 [M, W] with unit column
+    stride (any row stride), C <= W classes (default W; columns >= C are
+    padding, never read); labels int64 / int32 [M]; targets fp32 [M, >= C]."""
+    _dev(logits, labels, targets)
+    _rows_f32(logits, who)
+    M, W = logits.shape
+    C = W if C is None else int(C)
+    if not 1 <= C <= W:
+        raise ValueError(f"{who}: C={C} out of range for logits of {W} columns")
+    if M < 1:
+        raise ValueError(f"{who}: no rows")
+    if labels is None and targets is None:
+        raise ValueError(f"{who}: labels or targets must be given")
+    if labels is not None and (labels.dtype not in (torch.int64, torch.int32) or labels.shape != (M,)
+                               or not labels.is_contiguous()):
+        raise ValueError(f"{who}: labels must be contiguous int64 / int32 [M]")
+    if targets is not None:
+        _rows_f32(targets, who)
+        if targets.shape[0] != M or targets.shape[1] < C:
+            raise ValueError(f"{who}: targets must be [M, >= C]")
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"{who}: label_smoothing must be in [0, 1), got {label_smoothing}")
+    return dict(logits=logits.data_ptr(), ld=logits.stride(0), labels=_ptr(labels),
+                label_dtype=int(labels is not None and labels.dtype == torch.int64), soft_targets=int(targets is not None),
+                targets=_ptr(targets), ld_t=targets.stride(0) if targets is not None else 0, M=M, C=C,
+                label_smoothing=float(label_smoothing), loss_scale=float(loss_scale))
+
+
+def xent_fwd(logits, labels=None, targets=None, C=None, label_smoothing=0.0, loss_scale=1.0, want_rank=False,
+             row_loss=False) -> XentOut:
+    """F.cross_entropy(logits[:, :C], ..., label_smoothing=...) * loss_scale on the
+    fused fp32 kernel (include/maeclip.h "softmax cross-entropy"). targets (class
+    probabilities [M, C]) define the loss when given, else labels (class
+    indices [M]); with targets, labels only feed want_rank (the number of
+    classes ranked before the label, ties by index: top-k hit iff rank < k).
+    A label outside [0, C): loss term 0, rank C, the mean still over M rows."""
+    a = _xent_args("xent_fwd", logits, labels, targets, C, label_smoothing, loss_scale)
+    if want_rank and labels is None:
+        raise ValueError("xent_fwd: want_rank needs labels")
+    M = a["M"]
+    f32 = dict(device=logits.device, dtype=torch.float32)
+    loss = torch.empty((), **f32)
+    lse, lse_lo = torch.empty((2, M), **f32).unbind(0)
+    rank = torch.empty((M,), device=logits.device, dtype=torch.int32) if want_rank else None
+    rl = torch.empty((M,), **f32) if row_loss else None
+    ws_bytes = max(int(L.lib().maeclip_xent_workspace(M)), 16)
+    ws = torch.empty((ws_bytes // 4,), **f32)
+    args = L.XentArgs(loss=loss.data_ptr(), row_loss=_ptr(rl), lse=lse.data_ptr(), lse_lo=lse_lo.data_ptr(),
+                      rank=_ptr(rank), dlogits=None, ld_d=0, workspace=ws.data_ptr(), ws_bytes=ws_bytes, **a)
+    _call("maeclip_xent_fwd", _byref(args), _stream())
+    return XentOut(loss, lse, lse_lo, rank, rl)
+
+
+def xent_bwd(logits, lse, labels=None, targets=None, C=None, label_smoothing=0.0, loss_scale=1.0, grad_output=None,
+             out=None, lse_lo=None):
+    """d (grad_output * xent_fwd(...).loss) / d logits, one launch. lse / lse_lo:
+    xent_fwd's (lse_lo None: taken as 0, exact only while |logits| stays small);
+    grad_output: device f32 scalar (None: 1), read by the kernel -- no host
+    sync. out: fp32 [M, W'] with W' >= C (default: logits' shape), may be
+    logits itself; its columns C .. W' - 1 are set to zero."""
+    a = _xent_args("xent_bwd", logits, labels, targets, C, label_smoothing, loss_scale)
+    M = a["M"]
+    out = out if out is not None else torch.empty(tuple(logits.shape), device=logits.device, dtype=torch.float32)
+    _dev(out, lse, lse_lo, grad_output)
+    _rows_f32(out, "xent_bwd")
+    if out.shape[0] != M or out.shape[1] < a["C"]:
+        raise ValueError("xent_bwd: out must be [M, >= C]")
+    for name, t in (("lse", lse), ("lse_lo", lse_lo)):
+        if t is not None and (t.dtype != torch.float32 or t.shape != (M,) or not t.is_contiguous()):
+            raise ValueError(f"xent_bwd: {name} must be contiguous fp32 [M]")
+    if grad_output is not None and (grad_output.dtype != torch.float32 or grad_output.numel() != 1):
+        raise ValueError("xent_bwd: grad_output must be one f32 element")
+    # the kernel zero-fills to the row stride: for a column slice of a wider
+    # buffer that would reach into the neighbouring columns
+    if out.stride(0) != out.shape[1]:
+        raise ValueError("xent_bwd: out must be dense [M, W']")
+    args = L.XentArgs(loss=None, row_loss=None, lse=lse.data_ptr(), lse_lo=_ptr(lse_lo), rank=None,
+                      dlogits=out.data_ptr(), ld_d=out.stride(0), workspace=None, ws_bytes=0, **a)
+    _call("maeclip_xent_bwd", _byref(args), _ptr(grad_output), _stream())
+    return out
 
 
 # ------------------------------------------------------------ multi-tensor
