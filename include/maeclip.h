@@ -613,6 +613,128 @@ typedef struct {
 } maeclip_augment_args;
 int32_t maeclip_image_augment_u8(const maeclip_augment_args* args, void* stream);
 
+/* Mixup / CutMix on the device (mix.hip): timm's Mixup with correct_lam=True,
+ * no cutmix_minmax, partner of sample b = B - 1 - b (x.flip(0)), drawn from the
+ * device step like the crop above, so a replayed graph mixes anew every step.
+ *
+ * One record per sample; as int32 [B][8] it reads (kind, partner, x0, y0, x1,
+ * y1, bits of lam_pixel, bits of lam_target). kind: MAECLIP_MIX_NONE / _MIXUP /
+ * _CUTMIX. The box is [x0, x1) x [y0, y1) in pixels. lam_pixel weighs the own
+ * pixels of a mixup (1 otherwise); lam_target is the own label's weight.
+ *
+ * maeclip_mix_params draws the records. mode MAECLIP_MIX_BATCH: one draw for
+ * the whole call, key = MAECLIP_MIX_BATCH_KEY whatever sample_offset is, so
+ * every data-parallel rank draws the same mix; mode MAECLIP_MIX_ELEM: one draw
+ * per sample, key = sample_offset + b. All arithmetic is double, in exactly
+ * this order (mix.hip mc_mix_draw; no fused multiply-add); the fields start at
+ * 16, the crop draw uses 0 .. 4, so at equal seeds the two are independent:
+ *   step_seed = seed + (*step_ptr) * MAECLIP_STEP_MULT      (seed if NULL)
+ *   u(k, f)  = (mc_hash4(step_seed, key, k, f) >> 8) * 2^-24           in [0, 1)
+ *   uo(k, f) = ((mc_hash4(step_seed, key, k, f) >> 8) + 1) * 2^-24     in (0, 1]
+ *   record = (NONE, B-1-b, 0, 0, 0, 0, 1, 1)
+ *   if not u(0, 16) < prob: done
+ *   both alphas > 0: cutmix = u(0, 17) < switch_prob, alpha = its alpha
+ *   one alpha > 0  : that one (u(0, 17) is not looked at); none: done
+ *   lam ~ Beta(alpha, alpha):
+ *     alpha == 1: lam = u(0, 18)
+ *     else      : X = gamma(alpha, 0), Y = gamma(alpha, 1), lam = X / (X + Y)
+ *   gamma(a, g), Marsaglia-Tsang with Box-Muller normals, attempt t = 0 .. 15
+ *   at k = 16 g + t:
+ *     a' = a < 1 ? a + 1 : a;  d = a' - 1/3;  c = 1 / sqrt(9 d)   (1/3 = 1.0 / 3.0)
+ *     x = sqrt(-2 log(uo(k, 18))) * cos(6.283185307179586 * u(k, 19))
+ *     t1 = 1 + c x;  if t1 <= 0: next attempt
+ *     v = t1 t1 t1 = (t1 * t1) * t1
+ *     if log(uo(k, 20)) < 0.5 x x + d - d v + d log(v), evaluated
+ *        (((0.5 * x) * x + d) - d * v) + d * log(v): G = d v, stop
+ *     after 16 rejections: G = d (v = 1). An attempt is rejected with
+ *     probability < 0.05 for every a' >= 1, so this happens with probability
+ *     < 0.05^16 ~ 1.5e-21 per variate.
+ *     a < 1: G = G * exp(log(uo(16 g, 21)) / a)                     (the boost)
+ *   mixup : kind MIXUP, lam_pixel = lam_target = (float)lam
+ *   cutmix: r = sqrt(1 - lam), ch = (int)(H r), cw = (int)(W r)     (truncation)
+ *           cy = (int)floor(u(0, 22) H), cx = (int)floor(u(0, 23) W)
+ *           y0 = clip(cy - ch / 2, 0, H), y1 = clip(cy + ch / 2, 0, H), x0 / x1
+ *           likewise with cw, W (integer division; timm's rand_bbox)
+ *           kind CUTMIX, lam_pixel = 1,
+ *           lam_target = (float)(1 - (double)((x1 - x0) (y1 - y0)) / (double)(H W))
+ * Every loop above has a fixed bound, and 0 < X, Y < inf, so 0 <= lam <= 1.
+ * maeclip_mix_params_host evaluates the same function on the CPU: params and
+ * step_ptr are HOST pointers and nothing touches a device. log / exp / cos may
+ * differ in the last bit between the two: lam agrees to a few ulp, and a box
+ * can differ only where H r or W r lies within ~1e-13 of an integer.
+ * 0 <= B, 1 <= H, W <= 32768, alphas finite and >= 0, prob and switch_prob in [0, 1]. */
+#define MAECLIP_MIX_NONE 0
+#define MAECLIP_MIX_MIXUP 1
+#define MAECLIP_MIX_CUTMIX 2
+#define MAECLIP_MIX_BATCH 0
+#define MAECLIP_MIX_ELEM 1
+#define MAECLIP_MIX_BATCH_KEY 0x4d49584261746368ull /* "MIXBatch" */
+typedef struct {
+  int32_t kind, partner;
+  int32_t x0, y0, x1, y1;
+  float lam_pixel, lam_target;
+} maeclip_mix_record;
+typedef struct {
+  maeclip_mix_record* params;
+  int32_t B, H, W;
+  float mixup_alpha, cutmix_alpha, prob, switch_prob;
+  int32_t mode;
+  uint64_t seed, sample_offset;
+  const int64_t* step_ptr;
+} maeclip_mix_params_args;
+int32_t maeclip_mix_params(const maeclip_mix_params_args* args, void* stream);
+int32_t maeclip_mix_params_host(const maeclip_mix_params_args* args);
+
+/* dst = the batch mixed by `params` (device memory; maeclip_mix_params' or the
+ * caller's own), out of place: dst overlapping src is an argument error.
+ * dtype MAECLIP_MIX_U8: uint8 [B][S][S][3]; MAECLIP_MIX_F32: fp32 [B][3][S][S]
+ * -- the two forms maeclip_image_augment_u8 emits. Per element, a = the own
+ * sample's, p = the partner's (partner clamped to [0, B - 1]) at the same place:
+ *   kind NONE (and any kind not listed): a
+ *   kind CUTMIX: p where x0 <= x < x1 and y0 <= y < y1, a elsewhere, the box
+ *     clamped into [0, S] first (x1 <= x0 or y1 <= y0: empty); exact copies
+ *   kind MIXUP: v = fl32(fl32(lam a) + fl32(fl32(1 - lam) p)), lam = lam_pixel,
+ *     no fused multiply-add; fp32 stores v, uint8 stores rintf(v) (ties to
+ *     even; timm's FastCollateMixup), clamped to [0, 255] (a NaN gives 0)
+ * 16-byte loads and stores when src and dst are 16-byte aligned and a sample's
+ * extent in bytes is a multiple of 16 (S = 224: both dtypes); otherwise one
+ * element per access, the same bits. One launch, nothing allocated, no
+ * atomics: 2 reads + 1 write per element at most (a CUTMIX / NONE piece that
+ * lies wholly on one side reads one source only). 1 <= S <= 8192; fp32
+ * pointers 4-byte aligned. */
+#define MAECLIP_MIX_U8 0
+#define MAECLIP_MIX_F32 1
+typedef struct {
+  const void* src;
+  void* dst;
+  const maeclip_mix_record* params;
+  int64_t B, S;
+  int32_t dtype;
+} maeclip_mix_images_args;
+int32_t maeclip_mix_images(const maeclip_mix_images_args* args, void* stream);
+
+/* The class-probability targets of the mix: targets fp32 [B][ld_t], ld_t >= C,
+ *   t_bj = [j == y_b] lam_t + [j == y_p] fl32(1 - lam_t),   j < C
+ * with y = labels (int32: label_dtype 0, int64: 1), p = the record's partner
+ * (clamped to [0, B - 1]) and lam_t its lam_target; y_b == y_p gives exactly 1
+ * at that column. Columns C .. ld_t - 1 get zeros. A label outside [0, C)
+ * contributes nothing (as maeclip_xent_fwd treats one). Every thread computes
+ * its own columns: no zero-then-scatter, no barrier, no atomics, one launch.
+ * No label smoothing is applied here: maeclip_xent_fwd's eps is linear,
+ * t' = (1 - eps) t + eps / C, and it applies it to soft targets as well, so
+ * label_smoothing = eps there on these targets IS timm's mixup_target(eps) +
+ * SoftTargetCrossEntropy: (1 - eps) (lam 1[y_a] + (1 - lam) 1[y_p]) + eps / C =
+ * lam (on 1[y_a] + off) + (1 - lam) (on 1[y_p] + off), off = eps / C, on = 1 - eps. */
+typedef struct {
+  const void* labels;
+  int32_t label_dtype;
+  const maeclip_mix_record* params;
+  float* targets;
+  int64_t ld_t;
+  int64_t B, C;
+} maeclip_mix_targets_args;
+int32_t maeclip_mix_targets(const maeclip_mix_targets_args* args, void* stream);
+
 /* Retrieval (inference.py:40-45). l2_normalize replaces F.normalize(x, p=2,
  * dim=-1): y = x / max(||x||_2, eps), fp32 [M][P] rows (strides ldx / ldy).
  * topk_rows replaces torch.topk(dot_similarity, k) row-wise: s fp32 [Q][N]

@@ -172,6 +172,25 @@ class AugmentArgs(C.Structure):
                 ("mean", c_f32 * 3), ("std", c_f32 * 3), ("max_pixel", c_f32)]
 
 
+MIX_NONE, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2
+MIX_BATCH, MIX_ELEM = 0, 1
+
+
+class MixParamsArgs(C.Structure):
+    _fields_ = [("params", c_vp), ("B", c_i32), ("H", c_i32), ("W", c_i32),
+                ("mixup_alpha", c_f32), ("cutmix_alpha", c_f32), ("prob", c_f32), ("switch_prob", c_f32),
+                ("mode", c_i32), ("seed", c_u64), ("sample_offset", c_u64), ("step_ptr", c_vp)]
+
+
+class MixImagesArgs(C.Structure):
+    _fields_ = [("src", c_vp), ("dst", c_vp), ("params", c_vp), ("B", c_i64), ("S", c_i64), ("dtype", c_i32)]
+
+
+class MixTargetsArgs(C.Structure):
+    _fields_ = [("labels", c_vp), ("label_dtype", c_i32), ("params", c_vp), ("targets", c_vp), ("ld_t", c_i64),
+                ("B", c_i64), ("C", c_i64)]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "maeclip_abi_version": (c_i32, []),
@@ -199,6 +218,10 @@ _SIGS = {
     "maeclip_crop_params": (c_i32, [C.POINTER(CropParamsArgs), c_vp]),
     "maeclip_crop_params_host": (c_i32, [C.POINTER(CropParamsArgs)]),
     "maeclip_image_augment_u8": (c_i32, [C.POINTER(AugmentArgs), c_vp]),
+    "maeclip_mix_params": (c_i32, [C.POINTER(MixParamsArgs), c_vp]),
+    "maeclip_mix_params_host": (c_i32, [C.POINTER(MixParamsArgs)]),
+    "maeclip_mix_images": (c_i32, [C.POINTER(MixImagesArgs), c_vp]),
+    "maeclip_mix_targets": (c_i32, [C.POINTER(MixTargetsArgs), c_vp]),
     "maeclip_l2_normalize": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_f32, c_vp]),
     "maeclip_topk_rows": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "maeclip_sim_topk_splits": (c_i32, [c_i64, c_i64, c_i64, c_i32, c_i32]),

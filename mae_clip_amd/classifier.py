@@ -20,8 +20,11 @@ distributed.DataParallel take it unchanged. batch["target"] (class
 probabilities [B, num_classes], e.g. from Mixup / CutMix) replaces
 batch["label"] when present.
 
-Not here: Mixup / CutMix themselves, drop-path, layer-wise
-learning-rate decay, MAE's BatchNorm1d in front of the probe head and LARS.
+Mixup / CutMix are data.MixAugment (a CapturedStep transform that writes
+batch["target"]; label_smoothing here then gives timm's smoothed mix targets),
+layer-wise learning-rate decay is optim.layer_decay_param_groups (DESIGN.md
+Round 16). Not here: drop-path, MAE's BatchNorm1d in front of the probe head
+and LARS.
 """
 from __future__ import annotations
 

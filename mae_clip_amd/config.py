@@ -99,6 +99,14 @@ num_classes = 1000
 label_smoothing = 0.0              # F.cross_entropy's label_smoothing (MAE fine-tuning uses 0.1)
 classifier_trainable_encoder = False   # False: linear probe (frozen encoder, only the head trains); True: fine-tuning
 head_init_std = 0.02               # head.weight trunc-normal(std), head.bias zero (timm / MAE)
+# ---- Mixup / CutMix on the device (data.MixAugment); read by data.mix_augment_from_config() only. Both alphas 0:
+# off (the default). MAE's / timm's fine-tuning recipe: mixup_alpha 0.8, cutmix_alpha 1.0, label_smoothing 0.1.
+mixup_alpha = 0.0                  # Beta(alpha, alpha) of the mixup weight; 0: no mixup
+cutmix_alpha = 0.0                 # Beta(alpha, alpha) of the cutmix area; 0: no cutmix
+mix_prob = 1.0                     # probability that a draw mixes at all
+mix_switch_prob = 0.5              # probability of cutmix when both alphas are > 0
+mix_mode = "batch"                 # "batch": one draw per step; "elem": one per sample
+mix_seed = 4
 # ---- scheduling
 side_stream = True         # frozen text tower || image encoder; weight-gradient GEMMs || the dgrad chain
 # data parallel: encoder blocks per autograd Function, in forward order (the

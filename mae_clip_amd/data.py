@@ -16,6 +16,11 @@ A.RandomResizedCrop + A.HorizontalFlip on the device, box and coin drawn from
 the model's device step counter (maeclip_crop_params), pixels by
 maeclip_image_augment_u8; crop_params / crop_params_host / augment_images are
 its parts.
+
+Mixup / CutMix (timm's Mixup; nothing in the reference): MixAugment, drawn the
+same way (maeclip_mix_params), pixels by maeclip_mix_images, class-probability
+targets by maeclip_mix_targets; mix_params / mix_params_host / mix_images /
+mix_targets are its parts, Chain puts it behind TrainAugment.
 """
 from __future__ import annotations
 
@@ -224,6 +229,184 @@ def train_augment_from_config():
     if not CFG.augment:
         return None
     return TrainAugment(CFG.size, CFG.augment_scale, CFG.augment_ratio, CFG.augment_flip_p, CFG.augment_seed)
+
+
+# ------------------------------------------------------------ Mixup / CutMix
+_MIX_MODES = {"batch": L.MIX_BATCH, "elem": L.MIX_ELEM, L.MIX_BATCH: L.MIX_BATCH, L.MIX_ELEM: L.MIX_ELEM}
+
+
+def _mix_mode(mode, who):
+    if mode not in _MIX_MODES:
+        raise ValueError(f"{who}: mode must be 'batch' or 'elem' (timm's 'pair' is not built), got {mode!r}")
+    return _MIX_MODES[mode]
+
+
+def _mix_records(params, B, who):
+    if params is None or params.dtype != torch.int32 or params.shape != (B, 8) or not params.is_contiguous():
+        raise ValueError(f"{who}: params must be a dense int32 [B, 8] (B = {B})")
+    return params
+
+
+def mix_params(B, H, W, mixup_alpha=0.8, cutmix_alpha=1.0, prob=1.0, switch_prob=0.5, mode="batch", seed=0,
+               step_ptr=None, sample_offset=0, out=None, device=None):
+    """timm's Mixup draw (correct_lam, partner = B-1-b) for B samples of H x W
+    pixels, on the device from (seed, *step_ptr, and in mode "elem"
+    sample_offset + b; mode "batch": one draw for all, the same on every
+    data-parallel rank): int32 [B, 8] = (kind, partner, x0, y0, x1, y1, bits of
+    f32 lam_pixel, bits of f32 lam_target); kind 0 none, 1 mixup, 2 cutmix
+    (include/maeclip.h maeclip_mix_params). step_ptr: device int64 step counter
+    (None: step 0). The records live on `out`'s / step_ptr's / `device`."""
+    mode = _mix_mode(mode, "mix_params")
+    if out is not None:
+        _mix_records(out, B, "mix_params")
+    _dev(step_ptr, out)
+    if out is None:
+        dev = step_ptr.device if step_ptr is not None else device
+        if dev is None:
+            raise ValueError("mix_params: one of out, step_ptr or device says where to draw")
+        out = torch.empty((B, 8), device=dev, dtype=torch.int32)
+        _dev(out)
+    a = L.MixParamsArgs(params=out.data_ptr(), B=B, H=H, W=W, mixup_alpha=mixup_alpha, cutmix_alpha=cutmix_alpha,
+                        prob=prob, switch_prob=switch_prob, mode=mode, seed=int(seed), sample_offset=int(sample_offset),
+                        step_ptr=None if step_ptr is None else step_ptr.data_ptr())
+    _call("maeclip_mix_params", C.byref(a), _stream())
+    return out
+
+
+def mix_params_host(B, H, W, mixup_alpha=0.8, cutmix_alpha=1.0, prob=1.0, switch_prob=0.5, mode="batch", seed=0,
+                    step=0, sample_offset=0):
+    """The records mix_params draws at device step `step`, evaluated on the CPU
+    by the same function (no device needed): for logging, or to know step s's
+    mix on the host. -> CPU int32 [B, 8]; columns 6 and 7 .view(torch.float32)
+    are the two lams."""
+    mode = _mix_mode(mode, "mix_params_host")
+    out = torch.empty((B, 8), dtype=torch.int32)
+    step_v = C.c_int64(int(step))
+    a = L.MixParamsArgs(params=out.data_ptr(), B=B, H=H, W=W, mixup_alpha=mixup_alpha, cutmix_alpha=cutmix_alpha,
+                        prob=prob, switch_prob=switch_prob, mode=mode, seed=int(seed), sample_offset=int(sample_offset),
+                        step_ptr=C.addressof(step_v))
+    _call("maeclip_mix_params_host", C.byref(a))
+    return out
+
+
+def _mix_form(images, who):
+    """(B, S, library dtype) of a batch in one of the two forms the model takes"""
+    ok = torch.is_tensor(images) and images.dim() == 4 and images.is_contiguous()
+    if ok and images.dtype == torch.uint8 and images.shape[3] == 3 and images.shape[1] == images.shape[2]:
+        return images.shape[0], images.shape[1], 0
+    if ok and images.dtype == torch.float32 and images.shape[1] == 3 and images.shape[2] == images.shape[3]:
+        return images.shape[0], images.shape[2], 1
+    raise ValueError(f"{who}: images must be a dense uint8 [B, S, S, 3] or float32 [B, 3, S, S] batch")
+
+
+def mix_images(images, params, out=None):
+    """The batch mixed by `params` (device int32 [B, 8]; mix_params' or the
+    caller's own): kind 0 copies, 1 (mixup) writes lam a + (1 - lam) p in fp32
+    (uint8: rounded half to even), 2 (cutmix) takes the partner's pixels inside
+    the box (clamped into the image). images: uint8 [B, S, S, 3] or float32
+    [B, 3, S, S]; out: the same form, not overlapping `images` (out of place)."""
+    B, S, dt = _mix_form(images, "mix_images")
+    _mix_records(params, B, "mix_images")
+    if out is not None and (out.shape != images.shape or out.dtype != images.dtype or not out.is_contiguous()):
+        raise ValueError(f"mix_images: out must be a dense {images.dtype} {list(images.shape)}")
+    _dev(images, params, out)
+    if out is None:
+        out = torch.empty_like(images)
+    a = L.MixImagesArgs(src=images.data_ptr(), dst=out.data_ptr(), params=params.data_ptr(), B=B, S=S, dtype=dt)
+    _call("maeclip_mix_images", C.byref(a), _stream())
+    return out
+
+
+def mix_targets(labels, params, num_classes, out=None):
+    """Class-probability targets of the mix: float32 [B, num_classes] with
+    lam_target at the own label and 1 - lam_target at the partner's (exactly 1
+    where they coincide; a label outside [0, num_classes) contributes nothing).
+    No label smoothing here: ClassifierModel(label_smoothing=eps) / xent apply
+    it to soft targets, which is timm's mixup_target + SoftTargetCrossEntropy.
+    out: a dense float32 [B, ld_t], ld_t >= num_classes; its columns from
+    num_classes on get zeros."""
+    if not torch.is_tensor(labels) or labels.dim() != 1 or labels.dtype not in (torch.int64, torch.int32):
+        raise ValueError("mix_targets: labels must be int64 or int32 [B]")
+    labels = labels.contiguous()
+    B, Cn = labels.shape[0], int(num_classes)
+    _mix_records(params, B, "mix_targets")
+    if out is not None and (out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B or out.shape[1] < Cn
+                            or not out.is_contiguous()):
+        raise ValueError(f"mix_targets: out must be a dense float32 [B, ld_t] with ld_t >= C = {Cn}")
+    _dev(labels, params, out)
+    if out is None:
+        out = torch.empty((B, Cn), device=labels.device, dtype=torch.float32)
+    a = L.MixTargetsArgs(labels=labels.data_ptr(), label_dtype=int(labels.dtype == torch.int64),
+                         params=params.data_ptr(), targets=out.data_ptr(), ld_t=out.shape[1], B=B, C=Cn)
+    _call("maeclip_mix_targets", C.byref(a), _stream())
+    return out
+
+
+class MixAugment:
+    """timm's Mixup(mixup_alpha, cutmix_alpha, prob, switch_prob, mode,
+    correct_lam=True) on the device, drawn from the step counter like
+    TrainAugment, so it runs inside a captured step and mixes anew on every
+    replay. Label smoothing is the model's (ClassifierModel(label_smoothing=)).
+
+    __call__(batch, step_ptr, sample_offset=0) reads batch["image"] (uint8
+    [B, S, S, 3] or float32 [B, 3, S, S]) and batch["label"] and returns a new
+    dict with the mixed "image" and a "target" (float32 [B, num_classes]);
+    "label" and every other key pass through. Record, image and target buffers
+    are allocated once per (B, S, device, dtype) and reused: stable storage for
+    capture (`params` / `out` / `target` hold the last call's)."""
+
+    def __init__(self, num_classes, mixup_alpha=0.8, cutmix_alpha=1.0, prob=1.0, switch_prob=0.5, mode="batch",
+                 seed=None):
+        from . import config as CFG
+        self.num_classes = int(num_classes)
+        if self.num_classes < 1:
+            raise ValueError(f"MixAugment: num_classes must be >= 1, got {num_classes}")
+        self.mixup_alpha, self.cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
+        self.prob, self.switch_prob = float(prob), float(switch_prob)
+        self.mode = _mix_mode(mode, "MixAugment")
+        self.seed = int(CFG.mix_seed if seed is None else seed)
+        self._bufs = {}
+        self.params = self.out = self.target = None
+
+    def __call__(self, batch, step_ptr, sample_offset=0):
+        img, labels = batch["image"], batch["label"]
+        B, S, _ = _mix_form(img, "MixAugment")
+        key = (B, S, img.device, img.dtype)
+        if key not in self._bufs:
+            cpad = (self.num_classes + 3) // 4 * 4        # rows of whole 16-byte pieces
+            self._bufs[key] = (torch.empty((B, 8), device=img.device, dtype=torch.int32), torch.empty_like(img),
+                               torch.empty((B, cpad), device=img.device, dtype=torch.float32))
+        self.params, self.out, tpad = self._bufs[key]
+        mix_params(B, S, S, self.mixup_alpha, self.cutmix_alpha, self.prob, self.switch_prob, self.mode, self.seed,
+                   step_ptr, sample_offset, out=self.params)
+        mix_images(img, self.params, out=self.out)
+        mix_targets(labels, self.params, self.num_classes, out=tpad)
+        self.target = tpad[:, :self.num_classes]
+        out = dict(batch)
+        out["image"], out["target"] = self.out, self.target
+        return out
+
+
+class Chain:
+    """Transforms applied in order under TrainAugment's call contract:
+    Chain(TrainAugment(S), MixAugment(C))(batch, step_ptr, sample_offset)."""
+
+    def __init__(self, *transforms):
+        self.transforms = tuple(t for t in transforms if t is not None)
+
+    def __call__(self, batch, step_ptr, sample_offset=0):
+        for t in self.transforms:
+            batch = t(batch, step_ptr, sample_offset)
+        return batch
+
+
+def mix_augment_from_config():
+    """MixAugment of the config.mix* / *_alpha flags, or None when both alphas are 0 (the default)."""
+    from . import config as CFG
+    if not (CFG.mixup_alpha > 0 or CFG.cutmix_alpha > 0):
+        return None
+    return MixAugment(CFG.num_classes, CFG.mixup_alpha, CFG.cutmix_alpha, CFG.mix_prob, CFG.mix_switch_prob,
+                      CFG.mix_mode, CFG.mix_seed)
 
 
 def to_device_batch(images_u8, input_ids, attention_mask, device, non_blocking=True, augment=None, step_ptr=None,

@@ -32,6 +32,8 @@ max_grad_norm=c  torch.nn.utils.clip_grad_norm_(params, c) fused into the step:
 """
 from __future__ import annotations
 
+import re
+
 import torch
 
 from . import kernels as K
@@ -196,3 +198,46 @@ class AdamW(torch.optim.Optimizer):
             if "step" in st:
                 st["step"] = int(st["step"]) + delta
         self._dev_mirror += delta
+
+
+_BLOCK = re.compile(r"(?:^|\.)blocks\.(\d+)\.")
+_EMBED = re.compile(r"(?:^|\.)(?:cls_token$|pos_embed$|patch_embed\.)")
+_NO_DECAY = re.compile(r"(?:^|\.)(?:cls_token|pos_embed)$")
+
+
+def layer_decay_param_groups(model, lr, weight_decay, layer_decay):
+    """Parameter groups with layer-wise learning-rate decay, as MAE's
+    param_groups_lrd (BEiT's recipe): a parameter of layer id k trains at
+    lr * layer_decay ** (depth + 1 - k). Layer ids by parameter name, under any
+    prefix (ClassifierModel's `image_encoder.model.`): 0 for cls_token,
+    pos_embed and patch_embed.*; i + 1 for blocks.i.*; depth + 1 for everything
+    else (fc_norm, head), depth = the number of blocks. 1-D parameters (biases,
+    norm scales), cls_token and pos_embed go into groups with weight_decay 0.
+    Only parameters with requires_grad are included (a frozen encoder leaves
+    the head's groups); empty groups are not returned.
+
+    Every group carries "lr" (already scaled), "lr_scale", "weight_decay" and
+    "name" ("layer_<k>_decay" / "layer_<k>_no_decay"), ordered by layer id. A
+    scheduler sets group["lr"] = base_lr(step) * group["lr_scale"]. With
+    AdamW(device_lr=True) the rates live in one device array; a ViT-B gives
+    2 * 14 = 28 groups, one push_lr launch (<= 32)."""
+    if not 0.0 < float(layer_decay) <= 1.0:
+        raise ValueError(f"layer_decay must be in (0, 1], got {layer_decay}")
+    named = list(model.named_parameters())
+    blocks = [int(m.group(1)) for m in (_BLOCK.search(n) for n, _ in named) if m]
+    depth = max(blocks) + 1 if blocks else 0
+    groups = {}
+    for name, p in named:
+        if not p.requires_grad:
+            continue
+        m = _BLOCK.search(name)
+        k = int(m.group(1)) + 1 if m else (0 if _EMBED.search(name) else depth + 1)
+        no_decay = p.ndim == 1 or bool(_NO_DECAY.search(name))
+        key = (k, no_decay)
+        if key not in groups:
+            scale = float(layer_decay) ** (depth + 1 - k)
+            groups[key] = {"params": [], "lr": lr * scale, "lr_scale": scale,
+                           "weight_decay": 0.0 if no_decay else weight_decay,
+                           "name": f"layer_{k}_{'no_decay' if no_decay else 'decay'}"}
+        groups[key]["params"].append(p)
+    return [groups[key] for key in sorted(groups)]
