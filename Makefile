@@ -8,7 +8,7 @@ LIB := mae_clip_amd/libmaeclip.so
 
 all: $(LIB)
 
-build/obj/%.o: mae_clip_amd/csrc/%.hip mae_clip_amd/csrc/common.h mae_clip_amd/csrc/simtile.h include/maeclip.h
+build/obj/%.o: mae_clip_amd/csrc/%.hip $(wildcard mae_clip_amd/csrc/*.h) include/maeclip.h
 	@mkdir -p build/obj
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

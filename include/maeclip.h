@@ -208,8 +208,12 @@ int64_t maeclip_gemm_colsum_rows(int64_t M);
 /* scratch bytes maeclip_gemm may use for *args when args->splitk <= 1 (pass
  * them as args->workspace; a NULL workspace is always valid, just slower) */
 int64_t maeclip_gemm_workspace(const maeclip_gemm_args* args);
-/* which implementation maeclip_gemm runs for *args: always 0 = this library's
- * kernels (kept from ABI v9; the round-4 vendor-library path was removed) */
+/* which kernel family maeclip_gemm runs *args on: 0 = v1 (128x128 MFMA tiles:
+ * fp32 parity mode, odd K), 1 = the small fp32 kernel, 2 = v2 (LDS-DMA tiles),
+ * 4 = v4 (256-wide ping-pong tiles). The arguments are checked as maeclip_gemm
+ * checks them (-1 and a message if they fail; 0 for an empty output, which
+ * launches nothing); nothing is launched and no device is needed. MAECLIP_GEMM_VARIANT (1..7 a v2 tile, 8 = v4 then v2,
+ * 99 = v1) moves the answer as it moves the launch. */
 int32_t maeclip_gemm_impl(const maeclip_gemm_args* args);
 int32_t maeclip_gemm_splitk(int64_t M, int64_t N, int64_t K);
 

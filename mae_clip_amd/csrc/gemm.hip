@@ -23,35 +23,24 @@
 // MFMA: v_mfma_f32_16x16x32_bf16 (bf16) or v_mfma_f32_16x16x4_f32 (fp32
 //   parity mode, exact f32). The product is issued operand-swapped (B tile as
 //   the A operand) so each lane ends up owning 4 consecutive columns of one
-//   output row -> vectorised epilogue loads/stores along N.
-#include "common.h"
-#include "../../include/maeclip.h"
+//   output row -> vectorised epilogue loads/stores along N. That epilogue
+//   (frag_epilogue) and the bf16 fragment reader are shared with v2
+//   (gemm_common.h).
+//
+// This file also holds the public entry: the argument checks, the routing of a
+// call to one of the four kernel families (maeclip::gemm_route) and the
+// split-K reduction that v1, v2 and v4 share.
+#include "gemm_common.h"
 #include <stdlib.h>
-
-namespace maeclip {
-int gemm_v2(const maeclip_gemm_args& a, hipStream_t s, int variant);
-int gemm_v4(const maeclip_gemm_args& a, hipStream_t s);
-bool gemm_v4_ok(const maeclip_gemm_args& a);
-int check_q8(const maeclip_gemm_args& a, const char* who);
-int64_t gemm_v4_workspace(const maeclip_gemm_args& a);
-int gemm_small(const maeclip_gemm_args& a, hipStream_t s);
-bool gemm_small_ok(const maeclip_gemm_args& a);
-int64_t gemm_small_workspace(const maeclip_gemm_args& a);
-}
 
 namespace {
 
 constexpr int BM = 128, BN = 128, NT = 256;
 constexpr int TILE_BYTES = 16384;  // one operand, one stage
 
-enum { LAY_KC = 0, LAY_RC = 1 };
-enum { EPI_NONE = 0, EPI_GELU = 1, EPI_RESID = 2, EPI_DGELU = 3, EPI_GELU_D = 4, EPI_MUL_AUX = 5 };
-
 template <typename T> struct Tr;
 template <> struct Tr<bf16_t> { static constexpr int BK = 64; static constexpr int EPC = 8; };
 template <> struct Tr<float> { static constexpr int BK = 32; static constexpr int EPC = 4; };
-
-__device__ __forceinline__ int swz_rc(int k) { return ((k & 3) | (((k >> 3) & 1) << 2)) << 2; }
 
 // ---- staging: global -> registers (4 x 16 B per thread per operand)
 template <typename T, int LAY>
@@ -102,29 +91,10 @@ __device__ __forceinline__ void stage_store(char* lds, const v4u (&r)[4], int ti
 // ---- fragment: 8 consecutive k (k = 8*g + j, g = lane>>4) of tile row rs + (lane&15)
 template <typename T, int LAY> struct Frag;
 
-template <> struct Frag<bf16_t, LAY_KC> {
+template <int LAY> struct Frag<bf16_t, LAY> {
   v8s v;
   __device__ __forceinline__ void load(const char* lds, int rs, int ks, int lane) {
-    const int row = rs + (lane & 15);
-    const int chunk = 4 * ks + (lane >> 4);
-    v = *(const v8s*)(lds + row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4));
-  }
-};
-template <> struct Frag<bf16_t, LAY_RC> {
-  v8s v;
-  __device__ __forceinline__ void load(const char* lds, int rs, int ks, int lane) {
-    const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-    const int unit = (rs >> 2) + p;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int krow = 32 * ks + 8 * g + 4 * h + q;
-      const char* a = lds + krow * 256 + ((unit ^ swz_rc(krow)) << 3);
-      v4s t = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(v4s, a));
-      v[4 * h + 0] = t[0];
-      v[4 * h + 1] = t[1];
-      v[4 * h + 2] = t[2];
-      v[4 * h + 3] = t[3];
-    }
+    v = load_frag_bf16<LAY, 2 * BN>(lds, rs, ks, lane);  // RC rows of 128 bf16
   }
 };
 template <> struct Frag<float, LAY_KC> {
@@ -179,19 +149,13 @@ gemm_kernel(const maeclip_gemm_args args) {
 
   // XCD-aware remap: consecutive tiles (sharing A rows) land on one XCD.
   const int gm = (M + BM - 1) / BM, gn = (N + BN - 1) / BN;
-  const int nwg = gm * gn;
-  int bid = blockIdx.x;
-  {
-    const int q = nwg / 8, r = nwg % 8, x = bid % 8;
-    bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
-  }
+  const int bid = xcd_chunk_id(blockIdx.x, gm * gn);
   const int bm = bid / gn, bn = bid % gn;
   const int m0 = bm * BM, n0 = bn * BN;
 
   const int64_t z = blockIdx.z;
   const T* __restrict__ A = (const T*)args.A + z * args.strideA;
   const T* __restrict__ B = (const T*)args.B + z * args.strideB;
-  OutT* __restrict__ C = (OutT*)args.C + z * args.strideC;
 
   // stage s: A at smem + 2*s*TILE, B at smem + (2*s+1)*TILE
 #define LDS_A(s) (smem + (2 * (s)) * TILE_BYTES)
@@ -243,91 +207,8 @@ gemm_kernel(const maeclip_gemm_args args) {
     __syncthreads();
   }
 
-  // ---------------- epilogue: lane owns C[m][n..n+3]
-  const int g = lane >> 4;
-  if (S > 1) {  // split-K: raw fp32 partial tile -> workspace slab (reduced by splitk_reduce_kernel)
-    float* slab = args.workspace + ((int64_t)z * S + blockIdx.y) * (int64_t)M * N;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int m = m0 + wm * 64 + 16 * i + (lane & 15);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int n = n0 + wn * 64 + 16 * j + 4 * g;
-        if (m < M && n < N) *(v4f*)(slab + (int64_t)m * N + n) = acc[i][j] * args.alpha;
-      }
-    }
-    return;
-  }
-  const float alpha = args.alpha, beta = args.beta;
-  const float* __restrict__ bias = args.bias;
-  float csum[4][4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) csum[j][r] = 0.f;
-
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int m = m0 + wm * 64 + 16 * i + (lane & 15);
-    const bool mok = m < M;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = n0 + wn * 64 + 16 * j + 4 * g;
-      if (!mok || n >= N) continue;
-      v4f v = acc[i][j] * alpha;
-      if (bias) {
-        const v4f bb = *(const v4f*)(bias + n);
-        v += bb;
-      }
-      if (EPI == EPI_GELU) {
-        if (args.aux_out) st4<T>((T*)args.aux_out + z * args.strideC + (int64_t)m * args.ldaux + n, v);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = gelu_f(v[r]);
-      } else if (EPI == EPI_RESID) {
-        v += *(const v4f*)(args.resid + z * args.strideC + (int64_t)m * args.ldr + n);
-      } else if (EPI == EPI_DGELU) {
-        const v4f pre = ld4<T>((const T*)args.aux + z * args.strideC + (int64_t)m * args.ldaux + n);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] *= gelu_grad_f(pre[r]);
-        if (args.resid) v += *(const v4f*)(args.resid + z * args.strideC + (int64_t)m * args.ldr + n);
-      } else if (EPI == EPI_GELU_D) {
-        const v4f d = gelu4_inplace(v);
-        if (args.aux_out) st4<T>((T*)args.aux_out + z * args.strideC + (int64_t)m * args.ldaux + n, d);
-      } else if (EPI == EPI_MUL_AUX) {
-        v *= ld4<T>((const T*)args.aux + z * args.strideC + (int64_t)m * args.ldaux + n);
-        if (args.resid) v += *(const v4f*)(args.resid + z * args.strideC + (int64_t)m * args.ldr + n);
-      }
-      OutT* cp = C + (int64_t)m * args.ldc + n;
-      if (beta != 0.f) v += beta * ld4<OutT>(cp);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) csum[j][r] += v[r];
-      st4<OutT>(cp, v);
-    }
-  }
-  if (args.colsum_partial) {
-    // reduce over the 16 rows held by lanes sharing (lane>>4), then write one
-    // partial row per (block row, wave row): deterministic bias gradients.
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float s = csum[j][r];
-        s += __shfl_xor(s, 1, 64);
-        s += __shfl_xor(s, 2, 64);
-        s += __shfl_xor(s, 4, 64);
-        s += __shfl_xor(s, 8, 64);
-        csum[j][r] = s;
-      }
-    const int mrow = m0 + wm * 64;
-    if ((lane & 15) == 0 && mrow < M) {  // one partial row per 64-row group
-      float* prow = args.colsum_partial + ((int64_t)z * ((M + 63) / 64) + mrow / 64) * N;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int n = n0 + wn * 64 + 16 * j + 4 * g;
-        if (n < N) *(v4f*)(prow + n) = v4f{csum[j][0], csum[j][1], csum[j][2], csum[j][3]};
-      }
-    }
-  }
+  // lane owns C[m][n..n+3]; split-K slabs are reduced by splitk_reduce_kernel
+  frag_epilogue<T, OutT, EPI, 4, 4, false>(args, acc, S, m0, n0, wm, wn, lane);
 }
 
 // C[z] = sum_s slab[z][s] (+bias) (+beta*C), fixed summation order
@@ -371,99 +252,118 @@ int launch(const maeclip_gemm_args& a, hipStream_t s) {
   return 0;
 }
 
-template <typename T, typename OutT, int LA, int LB>
-int dispatch_epi(const maeclip_gemm_args& a, hipStream_t s) {
-  switch (a.epilogue) {
-    case EPI_NONE: return launch<T, OutT, LA, LB, EPI_NONE>(a, s);
-    case EPI_GELU: return launch<T, OutT, LA, LB, EPI_GELU>(a, s);
-    case EPI_RESID: return launch<T, OutT, LA, LB, EPI_RESID>(a, s);
-    case EPI_DGELU: return launch<T, OutT, LA, LB, EPI_DGELU>(a, s);
-    case EPI_GELU_D: return launch<T, OutT, LA, LB, EPI_GELU_D>(a, s);
-    case EPI_MUL_AUX: return launch<T, OutT, LA, LB, EPI_MUL_AUX>(a, s);
-  }
-  maeclip::set_error("maeclip_gemm: bad epilogue %d", a.epilogue);
-  return -1;
-}
 template <typename T, typename OutT>
-int dispatch_lay(const maeclip_gemm_args& a, hipStream_t s) {
-  if (a.a_layout == LAY_KC && a.b_layout == LAY_KC) return dispatch_epi<T, OutT, LAY_KC, LAY_KC>(a, s);
-  if (a.a_layout == LAY_KC && a.b_layout == LAY_RC) return dispatch_epi<T, OutT, LAY_KC, LAY_RC>(a, s);
-  if (a.a_layout == LAY_RC && a.b_layout == LAY_KC) return dispatch_epi<T, OutT, LAY_RC, LAY_KC>(a, s);
-  return dispatch_epi<T, OutT, LAY_RC, LAY_RC>(a, s);
+int gemm_v1(const maeclip_gemm_args& a, hipStream_t s) {
+  return dispatch_layouts(a, [&](auto la, auto lb) {
+    return dispatch_epilogue(a, "maeclip_gemm", [&](auto epi) {
+      return launch<T, OutT, decltype(la)::value, decltype(lb)::value, decltype(epi)::value>(a, s);
+    });
+  });
 }
 
-}  // namespace
+// MAECLIP_GEMM_VARIANT, read once: 0 / unset = the dispatcher's own choice,
+// 1..7 pins a v2 tile (gemm_v2), 8 = v4 with v2's own tile choice behind it, 99 = v1
+int forced_variant() {
+  static const int forced = getenv("MAECLIP_GEMM_VARIANT") ? atoi(getenv("MAECLIP_GEMM_VARIANT")) : 0;
+  return forced;
+}
 
-extern "C" int32_t maeclip_gemm(const maeclip_gemm_args* a, void* stream) {
-  MC_CHECK_ARG(a != nullptr, "maeclip_gemm: null args");
-  MC_CHECK_ARG(a->M >= 0 && a->N >= 0 && a->K >= 0 && a->batch >= 1, "maeclip_gemm: bad sizes");
-  if (a->M == 0 || a->N == 0) return 0;
-  MC_CHECK_ARG(a->M < (1ll << 31) && a->N < (1ll << 31) && a->K < (1ll << 31), "maeclip_gemm: dims too large");
-  MC_CHECK_ARG(a->dtype == MAECLIP_F32 || a->dtype == MAECLIP_BF16, "maeclip_gemm: bad dtype %d", a->dtype);
-  MC_CHECK_ARG(a->out_dtype == MAECLIP_F32 || a->out_dtype == MAECLIP_BF16, "maeclip_gemm: bad out dtype");
-  // every path switches on the epilogue with a default: an unknown value would
-  // run another epilogue's kernel (DGELU / MUL_AUX with a null aux)
-  MC_CHECK_ARG(a->epilogue >= EPI_NONE && a->epilogue <= EPI_MUL_AUX, "maeclip_gemm: bad epilogue %d", a->epilogue);
+// The argument checks of maeclip_gemm (and of maeclip_gemm_impl, which names
+// itself in the messages): 0 = a valid call, -1 = rejected, message set.
+// *empty: the output is empty (M or N = 0); such a call is valid without the
+// checks that follow the sizes, and a no-op.
+int check_args(const maeclip_gemm_args* a, const char* who, bool* empty) {
+  *empty = false;
+  MC_CHECK_ARG(a != nullptr, "%s: null args", who);
+  MC_CHECK_ARG(a->M >= 0 && a->N >= 0 && a->K >= 0 && a->batch >= 1, "%s: bad sizes", who);
+  *empty = a->M == 0 || a->N == 0;
+  if (*empty) return 0;
+  MC_CHECK_ARG(a->M < (1ll << 31) && a->N < (1ll << 31) && a->K < (1ll << 31), "%s: dims too large", who);
+  MC_CHECK_ARG(a->dtype == MAECLIP_F32 || a->dtype == MAECLIP_BF16, "%s: bad dtype %d", who, a->dtype);
+  MC_CHECK_ARG(a->out_dtype == MAECLIP_F32 || a->out_dtype == MAECLIP_BF16, "%s: bad out dtype", who);
+  MC_CHECK_ARG(a->epilogue >= EPI_NONE && a->epilogue <= EPI_MUL_AUX, "%s: bad epilogue %d", who, a->epilogue);
   const int epc = a->dtype == MAECLIP_BF16 ? 8 : 4;
   // 16-B vector loads along the contiguous dimension of each operand
   MC_CHECK_ARG(a->a_layout == LAY_KC ? (a->K % epc == 0 && a->lda % epc == 0)
                                      : (a->M % epc == 0 && a->lda % epc == 0),
-               "maeclip_gemm: A contiguous dim / lda must be a multiple of %d", epc);
+               "%s: A contiguous dim / lda must be a multiple of %d", who, epc);
   MC_CHECK_ARG(a->b_layout == LAY_KC ? (a->K % epc == 0 && a->ldb % epc == 0)
                                      : (a->N % epc == 0 && a->ldb % epc == 0),
-               "maeclip_gemm: B contiguous dim / ldb must be a multiple of %d", epc);
-  MC_CHECK_ARG(a->N % 4 == 0 && a->ldc % 4 == 0, "maeclip_gemm: N and ldc must be multiples of 4");
+               "%s: B contiguous dim / ldb must be a multiple of %d", who, epc);
+  MC_CHECK_ARG(a->N % 4 == 0 && a->ldc % 4 == 0, "%s: N and ldc must be multiples of 4", who);
   MC_CHECK_ARG(((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->B & 15) == 0 && ((uintptr_t)a->C & 7) == 0,
-               "maeclip_gemm: operands must be 16-byte aligned");
+               "%s: operands must be 16-byte aligned", who);
   MC_CHECK_ARG((a->epilogue != EPI_DGELU && a->epilogue != EPI_MUL_AUX) || a->aux,
-               "maeclip_gemm: DGELU / MUL_AUX epilogue needs aux");
+               "%s: DGELU / MUL_AUX epilogue needs aux", who);
   MC_CHECK_ARG(a->epilogue != EPI_RESID || (a->resid && a->out_dtype == MAECLIP_F32),
-               "maeclip_gemm: RESID epilogue needs fp32 resid and fp32 output");
+               "%s: RESID epilogue needs fp32 resid and fp32 output", who);
   if (a->splitk > 1) {
     MC_CHECK_ARG(a->workspace && a->epilogue == EPI_NONE && !a->colsum_partial && a->splitk <= 64,
-                 "maeclip_gemm: split-K needs a workspace, epilogue 0 and no colsum");
-    MC_CHECK_ARG(a->ldc == a->N, "maeclip_gemm: split-K output must be dense (ldc == N)");
+                 "%s: split-K needs a workspace, epilogue 0 and no colsum", who);
+    MC_CHECK_ARG(a->ldc == a->N, "%s: split-K output must be dense (ldc == N)", who);
   }
-  if (int e = maeclip::check_q8(*a, "maeclip_gemm")) return e;
+  return maeclip::check_q8(*a, who);
+}
+
+}  // namespace
+
+namespace maeclip {
+// Which kernel family a (checked) call runs on; host arithmetic on the
+// arguments only, no device query.
+//   SMALL: small fp32 outputs (gemm_small_ok)
+//   V4:    8-wave ping-pong 256x256 / 192x256 / 128x256 tiles, persistent,
+//          buffer-descriptor DMA, wherever its shape conditions hold (gemm_v4_ok)
+//   V2:    LDS-DMA, 128- / 256-wide tiles: every other bf16 shape with 64-aligned K
+//   V1:    the rest (fp32 parity mode, odd K)
+GemmRoute gemm_route(const maeclip_gemm_args& a) {
+  const int forced = forced_variant();
+  if (forced != 99 && gemm_small_ok(a)) return GemmRoute::SMALL;
+  if ((forced == 0 || forced == 8) && gemm_v4_ok(a)) return GemmRoute::V4;
+  if (a.dtype == MAECLIP_BF16 && forced != 99 && a.K % 64 == 0 && a.K > 0 && a.lda % 8 == 0 && a.ldb % 8 == 0 &&
+      (a.a_layout == LAY_KC || a.M >= 8) && (a.b_layout == LAY_KC || a.N >= 8))
+    return GemmRoute::V2;
+  return GemmRoute::V1;
+}
+}  // namespace maeclip
+
+extern "C" int32_t maeclip_gemm(const maeclip_gemm_args* a, void* stream) {
+  using maeclip::GemmRoute;
+  bool empty;
+  if (int e = check_args(a, "maeclip_gemm", &empty)) return e;
+  if (empty) return 0;
   hipStream_t s = (hipStream_t)stream;
-  // v2 (LDS-DMA, larger tiles) for every bf16 shape with 64-aligned K
-  static const int forced = getenv("MAECLIP_GEMM_VARIANT") ? atoi(getenv("MAECLIP_GEMM_VARIANT")) : 0;
-  // v4/v2 write raw fp32 split-K slabs and leave the reduction to
-  // splitk_reduce (v1's launch() reduces by itself)
-  if (forced != 99 && maeclip::gemm_small_ok(*a)) return maeclip::gemm_small(*a, s);
-  int rc = 1;
-  // v4 (8-wave ping-pong 256x256 / 192x256, persistent, buffer-descriptor DMA,
-  // split tiles with an in-launch fix-up when the tiles leave most of the grid
-  // idle) wherever its shape conditions hold; MAECLIP_GEMM_VARIANT=1..7 pins a
-  // v2 tile, 99 v1
-  const bool v4 = (forced == 0 || forced == 8) && maeclip::gemm_v4_ok(*a);
+  const GemmRoute route = maeclip::gemm_route(*a);
+  if (route == GemmRoute::SMALL) return maeclip::gemm_small(*a, s);
   // every path but v4 (whose epilogue writes it): the fp8-blocks copy of C
   // (q8) by a second pass
-  if (a->q8 && !v4) {
+  if (a->q8 && route != GemmRoute::V4) {
     maeclip_gemm_args b = *a;
     b.q8 = nullptr;
     if (int e = maeclip_gemm(&b, stream)) return e;
     return maeclip_quant_blocks_fp8(a->C, MAECLIP_BF16, a->M, a->N, a->ldc, a->q8, a->ldq8, a->q8_scale, a->q8_fmt,
                                     stream);
   }
-  if (v4)
-    rc = maeclip::gemm_v4(*a, s);
-  else if (a->dtype == MAECLIP_BF16 && forced != 99 && a->K % 64 == 0 && a->K > 0 && a->lda % 8 == 0 && a->ldb % 8 == 0 &&
-           (a->a_layout == LAY_KC || a->M >= 8) && (a->b_layout == LAY_KC || a->N >= 8))
-    rc = maeclip::gemm_v2(*a, s, forced == 8 ? 0 : forced);
-  if (rc != 1) return (rc == 0 && a->splitk > 1) ? splitk_reduce(*a, s) : rc;
+  if (route == GemmRoute::V4 || route == GemmRoute::V2) {
+    const int forced = forced_variant();
+    const int rc = route == GemmRoute::V4 ? maeclip::gemm_v4(*a, s) : maeclip::gemm_v2(*a, s, forced == 8 ? 0 : forced);
+    // v4 / v2 write raw fp32 split-K slabs and leave the reduction to
+    // splitk_reduce (v1's launch() reduces by itself)
+    return (rc == 0 && a->splitk > 1) ? splitk_reduce(*a, s) : rc;
+  }
   if (a->dtype == MAECLIP_BF16)
-    return a->out_dtype == MAECLIP_BF16 ? dispatch_lay<bf16_t, bf16_t>(*a, s) : dispatch_lay<bf16_t, float>(*a, s);
-  return a->out_dtype == MAECLIP_BF16 ? dispatch_lay<float, bf16_t>(*a, s) : dispatch_lay<float, float>(*a, s);
+    return a->out_dtype == MAECLIP_BF16 ? gemm_v1<bf16_t, bf16_t>(*a, s) : gemm_v1<bf16_t, float>(*a, s);
+  return a->out_dtype == MAECLIP_BF16 ? gemm_v1<float, bf16_t>(*a, s) : gemm_v1<float, float>(*a, s);
 }
 
 extern "C" int64_t maeclip_gemm_colsum_rows(int64_t M) { return (M + 63) / 64; }
 
-// Every GEMM runs on this library's kernels (ABI v9 kept the query; the
-// round-4 vendor path was removed in round 5).
+// The route of *args (maeclip::GemmRoute as a number) after maeclip_gemm's
+// argument checks; launches nothing and needs no device. An empty output runs
+// on no kernel: 0.
 extern "C" int32_t maeclip_gemm_impl(const maeclip_gemm_args* a) {
-  (void)a;
-  return 0;
+  bool empty;
+  if (int e = check_args(a, "maeclip_gemm_impl", &empty)) return e;
+  return empty ? 0 : (int32_t)maeclip::gemm_route(*a);
 }
 
 // Scratch bytes maeclip_gemm may use for this call when the caller asks for no
@@ -473,8 +373,8 @@ extern "C" int32_t maeclip_gemm_impl(const maeclip_gemm_args* a) {
 // before the first launch, and every completed launch leaves them zero).
 extern "C" int64_t maeclip_gemm_workspace(const maeclip_gemm_args* a) {
   if (!a || a->splitk > 1) return 0;
-  static const int forced = getenv("MAECLIP_GEMM_VARIANT") ? atoi(getenv("MAECLIP_GEMM_VARIANT")) : 0;
-  if (forced != 99 && maeclip::gemm_small_ok(*a)) return maeclip::gemm_small_workspace(*a);
+  if (maeclip::gemm_route(*a) == maeclip::GemmRoute::SMALL) return maeclip::gemm_small_workspace(*a);
+  const int forced = forced_variant();
   return (forced == 0 || forced == 8) ? maeclip::gemm_v4_workspace(*a) : 0;
 }
 

@@ -26,22 +26,14 @@
 // Ping-pong: group 1 (wm == 1) executes one extra barrier up front, so in every
 // barrier-delimited segment one group issues its ds_reads/DMA while the other
 // group's 16 MFMAs run (one wave of each group per SIMD).
-#include "common.h"
+//
+// The layout / epilogue values, their host dispatch and the RC swizzle come
+// from gemm_common.h; the epilogue (epilogue4: LDS-transposed 16-row chunks
+// with prefetch rings) is this file's own.
+#include "gemm_common.h"
 #include <stdlib.h>
-#include "../../include/maeclip.h"
-
-namespace maeclip {
-int check_q8(const maeclip_gemm_args& a, const char* who);
-}
 
 namespace {
-
-enum { LAY_KC = 0, LAY_RC = 1 };
-enum { EPI_NONE = 0, EPI_GELU = 1, EPI_RESID = 2, EPI_DGELU = 3, EPI_GELU_D = 4, EPI_MUL_AUX = 5 };
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ int swz_rc(int k) { return ((k & 3) | (((k >> 3) & 1) << 2)) << 2; }
 
 #ifndef GEMM4_EPI_PF_AUX
 #define GEMM4_EPI_PF_AUX 2
@@ -1376,14 +1368,8 @@ int epi4(const maeclip_gemm_args& a, hipStream_t s) {
 #endif
   return launch4<LA, LB, OutT, GEMM4_DEV_EPI>(a, s);
 #else
-  switch (a.epilogue) {
-    case EPI_NONE: return launch4<LA, LB, OutT, EPI_NONE>(a, s);
-    case EPI_GELU: return launch4<LA, LB, OutT, EPI_GELU>(a, s);
-    case EPI_RESID: return launch4<LA, LB, OutT, EPI_RESID>(a, s);
-    case EPI_GELU_D: return launch4<LA, LB, OutT, EPI_GELU_D>(a, s);
-    case EPI_MUL_AUX: return launch4<LA, LB, OutT, EPI_MUL_AUX>(a, s);
-    default: return launch4<LA, LB, OutT, EPI_DGELU>(a, s);
-  }
+  return dispatch_epilogue(a, "maeclip_gemm(v4)",
+                           [&](auto epi) { return launch4<LA, LB, OutT, decltype(epi)::value>(a, s); });
 #endif
 }
 
@@ -1439,10 +1425,7 @@ int64_t gemm_v4_workspace(const maeclip_gemm_args& a) {
 }
 
 int gemm_v4(const maeclip_gemm_args& a, hipStream_t s) {
-  if (a.a_layout == LAY_KC && a.b_layout == LAY_KC) return out4<LAY_KC, LAY_KC>(a, s);
-  if (a.a_layout == LAY_KC && a.b_layout == LAY_RC) return out4<LAY_KC, LAY_RC>(a, s);
-  if (a.a_layout == LAY_RC && a.b_layout == LAY_KC) return out4<LAY_RC, LAY_KC>(a, s);
-  return out4<LAY_RC, LAY_RC>(a, s);
+  return dispatch_layouts(a, [&](auto la, auto lb) { return out4<decltype(la)::value, decltype(lb)::value>(a, s); });
 }
 }  // namespace maeclip
 
@@ -1484,14 +1467,8 @@ int epi_f8(const maeclip_gemm_args& a, const float* sa, const float* sb, hipStre
 #ifdef GEMM4_DEV_SUBSET
   return launch_f8<OutT, EPI_NONE, F8>(a, sa, sb, s);
 #else
-  switch (a.epilogue) {
-    case EPI_NONE: return launch_f8<OutT, EPI_NONE, F8>(a, sa, sb, s);
-    case EPI_GELU: return launch_f8<OutT, EPI_GELU, F8>(a, sa, sb, s);
-    case EPI_RESID: return launch_f8<OutT, EPI_RESID, F8>(a, sa, sb, s);
-    case EPI_GELU_D: return launch_f8<OutT, EPI_GELU_D, F8>(a, sa, sb, s);
-    case EPI_MUL_AUX: return launch_f8<OutT, EPI_MUL_AUX, F8>(a, sa, sb, s);
-    default: return launch_f8<OutT, EPI_DGELU, F8>(a, sa, sb, s);
-  }
+  return dispatch_epilogue(a, "maeclip_gemm_fp8",
+                           [&](auto epi) { return launch_f8<OutT, decltype(epi)::value, F8>(a, sa, sb, s); });
 #endif
 }
 
@@ -1512,13 +1489,13 @@ int launch_f8b(const maeclip_gemm_args& a, const uint8_t* sab, const float* sb, 
 
 template <typename OutT, int F8>
 int epi_f8b(const maeclip_gemm_args& a, const uint8_t* sab, const float* sb, hipStream_t s) {
-  switch (a.epilogue) {
-    case EPI_NONE: return launch_f8b<OutT, EPI_NONE, F8>(a, sab, sb, s);
-    case EPI_RESID: return launch_f8b<OutT, EPI_RESID, F8>(a, sab, sb, s);
-    case EPI_GELU_D: return launch_f8b<OutT, EPI_GELU_D, F8>(a, sab, sb, s);
-    case EPI_MUL_AUX: return launch_f8b<OutT, EPI_MUL_AUX, F8>(a, sab, sb, s);
-    default: MC_CHECK_ARG(false, "maeclip_gemm_fp8_blocks: epilogue %d not built (0, 2, 4, 5)", a.epilogue);
-  }
+  return dispatch_epilogue(a, "maeclip_gemm_fp8_blocks", [&](auto epi) -> int {
+    constexpr int EPI = decltype(epi)::value;
+    if constexpr (EPI == EPI_GELU || EPI == EPI_DGELU)
+      MC_CHECK_ARG(false, "maeclip_gemm_fp8_blocks: epilogue %d not built (0, 2, 4, 5)", a.epilogue);
+    else
+      return launch_f8b<OutT, EPI, F8>(a, sab, sb, s);
+  });
 }
 
 // argument checks shared by the two fp8 entries

@@ -7,14 +7,12 @@
 // 64-192 workgroups; each K-chunk of 32 is staged k-major through LDS (padded
 // rows, no bank conflicts on the broadcast reads) and every thread does 4 FMA
 // per k. Epilogues and their semantics are those of gemm.hip (bias, GELU with
-// pre-activation aux_out, residual, dGELU, GELU', mul-aux, alpha/beta).
-#include "common.h"
-#include "../../include/maeclip.h"
+// pre-activation aux_out, residual, dGELU, GELU', mul-aux, alpha/beta), one
+// value per thread (epi_store); the layout / epilogue values and their
+// dispatch come from gemm_common.h.
+#include "gemm_common.h"
 
 namespace {
-
-enum { LAY_KC = 0, LAY_RC = 1 };
-enum { EPI_NONE = 0, EPI_GELU = 1, EPI_RESID = 2, EPI_DGELU = 3, EPI_GELU_D = 4, EPI_MUL_AUX = 5 };
 
 constexpr int TS = 32;   // tile edge (m, n and k chunk)
 
@@ -152,17 +150,6 @@ int launch_small(const maeclip_gemm_args& a, hipStream_t s) {
   }
   return 0;
 }
-template <int LA, int LB>
-int epi_small(const maeclip_gemm_args& a, hipStream_t s) {
-  switch (a.epilogue) {
-    case EPI_NONE: return launch_small<LA, LB, EPI_NONE>(a, s);
-    case EPI_GELU: return launch_small<LA, LB, EPI_GELU>(a, s);
-    case EPI_RESID: return launch_small<LA, LB, EPI_RESID>(a, s);
-    case EPI_DGELU: return launch_small<LA, LB, EPI_DGELU>(a, s);
-    case EPI_GELU_D: return launch_small<LA, LB, EPI_GELU_D>(a, s);
-    default: return launch_small<LA, LB, EPI_MUL_AUX>(a, s);
-  }
-}
 
 }  // namespace
 
@@ -182,9 +169,10 @@ int64_t gemm_small_workspace(const maeclip_gemm_args& a) {
 }
 
 int gemm_small(const maeclip_gemm_args& a, hipStream_t s) {
-  if (a.a_layout == LAY_KC && a.b_layout == LAY_KC) return epi_small<LAY_KC, LAY_KC>(a, s);
-  if (a.a_layout == LAY_KC && a.b_layout == LAY_RC) return epi_small<LAY_KC, LAY_RC>(a, s);
-  if (a.a_layout == LAY_RC && a.b_layout == LAY_KC) return epi_small<LAY_RC, LAY_KC>(a, s);
-  return epi_small<LAY_RC, LAY_RC>(a, s);
+  return dispatch_layouts(a, [&](auto la, auto lb) {
+    return dispatch_epilogue(a, "maeclip_gemm(small f32)", [&](auto epi) {
+      return launch_small<decltype(la)::value, decltype(lb)::value, decltype(epi)::value>(a, s);
+    });
+  });
 }
 }  // namespace maeclip

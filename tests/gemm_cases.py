@@ -101,8 +101,9 @@ def predict(c):
     """the dispatcher restated: gemm_small_ok, gemm_v4_ok, the v2 line, else v1 (operands of the harness are
     16-byte aligned, which v4 also asks of C, aux, resid, bias and the split-K workspace). This is the test's
     own reading of gemm.hip compared with the case's own label: it keeps the table honest about which kernel
-    a case is written for, but it does not ask the library and cannot notice a dispatcher change by itself.
-    Only the maeclip_gemm_workspace assertions (gemm_small's K split, the v4 split plan) query the library."""
+    a case is written for. The library's own answer, maeclip_gemm_impl (maeclip::gemm_route, the function
+    maeclip_gemm routes by), is checked against the same labels in test_gemm_cases_cpu.py, so a dispatcher
+    change that moves a case shows there; this restatement stays independent of it."""
     g = geometry(c)
     if c.dt == F32:
         small = c.out == F32 and c.S <= 1 and not c.colsum and c.M * c.N <= 256 * 1024 and c.K <= 8192

@@ -5,6 +5,7 @@ its checks would fail differently ("launch failed", return -2), which is why
 each case also looks at the message. The kernels themselves are compared with
 fp64 references in test_gemm_reference_gpu.py."""
 import ctypes
+import os
 
 import pytest
 
@@ -88,6 +89,18 @@ def test_gemm_rejects(lib, name):
 
 def test_gemm_rejects_null_args(lib):
     _rejected(lib, None, b"maeclip_gemm: null args")
+
+
+def test_gemm_impl_checks_like_gemm(lib):
+    """the route query runs maeclip_gemm's argument checks first: -1 and a message of its own"""
+    for a, what in ((_args(epilogue=6), b"bad epilogue 6"), (_args(epilogue=-1), b"bad epilogue -1"),
+                    (None, b"null args"), (_args(K=6), b"A contiguous dim")):
+        rc = lib.maeclip_gemm_impl(ctypes.byref(a) if a is not None else None)
+        msg = lib.maeclip_last_error()
+        assert rc == -1 and msg.startswith(b"maeclip_gemm_impl: ") and what in msg, (rc, msg)
+    assert lib.maeclip_gemm_impl(ctypes.byref(_args(M=0))) == 0   # an empty output: valid, runs on no kernel
+    if os.environ.get("MAECLIP_GEMM_VARIANT", "0").strip() in ("", "0"):     # a pinned variant moves the route
+        assert lib.maeclip_gemm_impl(ctypes.byref(_args())) == 1   # the valid small fp32 call: gemm_small
 
 
 def test_gemm_empty_output_is_a_no_op(lib):

@@ -2,6 +2,8 @@
 case is legal and predicted onto the path it is meant for, its reference is
 finite, its bound is meaningful (E32 > 0) and, for a bf16 output, tight enough
 to tell round-to-nearest-even from truncation."""
+import os
+
 import pytest
 import torch
 
@@ -44,6 +46,23 @@ def test_case_table(group):
             if dt == torch.bfloat16:
                 err = (_truncate_bf16(r64) - r64).abs()
                 assert (err > _bf16_half_ulp(r64, FACTOR * e32) + FACTOR * e32).any(), (c.id, name, "truncation passes")
+
+
+ROUTE = {"v1f": 0, "v1b": 0, "small": 1, "v2": 2, "v4": 4}    # maeclip::GemmRoute
+# the library reads MAECLIP_GEMM_VARIANT once per process and routes by it: the labels hold for the default only
+PINNED = os.environ.get("MAECLIP_GEMM_VARIANT", "0").strip() not in ("", "0")
+
+
+@pytest.mark.skipif(PINNED, reason="MAECLIP_GEMM_VARIANT pins a GEMM path in this environment")
+@pytest.mark.parametrize("group", list(GROUPS))
+def test_library_routes_every_case_to_its_path(group):
+    """maeclip_gemm_impl (host arithmetic only: no launch, no device) against the label of every case"""
+    import ctypes
+    from mae_clip_amd import _lib as L
+    lib = L.lib()
+    for c in GROUPS[group]():
+        a = G.gemm_args(c)
+        assert lib.maeclip_gemm_impl(ctypes.byref(a)) == ROUTE[c.path], (c.id, lib.maeclip_last_error())
 
 
 def test_total_is_a_few_hundred():
