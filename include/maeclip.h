@@ -297,6 +297,16 @@ typedef struct {
 } maeclip_attn_args;
 int32_t maeclip_attn_fwd(const maeclip_attn_args* args, void* stream);
 int32_t maeclip_attn_bwd(const maeclip_attn_args* args, void* stream);
+/* The kernel maeclip_attn_fwd (bwd = 0) / maeclip_attn_bwd (bwd != 0) runs *args
+ * on, after their argument checks and under the options set (-1 and the message
+ * for a call they reject); nothing is launched and no device is needed:
+ *   0 resident forward, 1 resident forward with 16 waves, 2 backward with four
+ *   LDS images (fp32: the two-phase backward), 3 backward with two images, 4 two
+ *   images at 3 workgroups per CU, 5 backward with key_mask / dropout, 6 diagonal
+ *   backward, 7 16-wave backward, 8 fp32 rows, 9 streamed, 10 backward 2, 3 or 4
+ *   by occupancy (bf16 with ATTN_TWO unset: the one choice that asks the device,
+ *   made at the launch). */
+int32_t maeclip_attn_impl(const maeclip_attn_args* args, int32_t bwd);
 
 /* ------------------------------------------------------------- LayerNorm
  * Replaces nn.LayerNorm (timm norm1/norm2/fc_norm, modules.py:67, DistilBERT

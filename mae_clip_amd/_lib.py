@@ -230,6 +230,7 @@ _SIGS = {
                                  c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "maeclip_attn_fwd": (c_i32, [C.POINTER(AttnArgs), c_vp]),
     "maeclip_attn_bwd": (c_i32, [C.POINTER(AttnArgs), c_vp]),
+    "maeclip_attn_impl": (c_i32, [C.POINTER(AttnArgs), c_i32]),
     "maeclip_ln_fwd": (c_i32, [C.POINTER(LnFwdArgs), c_vp]),
     "maeclip_ln_bwd": (c_i32, [C.POINTER(LnBwdArgs), c_vp]),
     "maeclip_ln_bwd_partial_rows": (c_i32, [c_i64, c_i64]),

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from mae_clip_amd import kernels as K
+from tests import attn_cases as A
 from tests.helpers import build_pair, make_batch, product_config, record_parity, same_bits
 
 pytestmark = pytest.mark.gpu
@@ -108,6 +109,10 @@ def test_long_sequences_run_by_default(dev, shape):
     """no option set: forward, backward and bias partials against fp64. Before
     the streamed kernels these calls were rejected ("needs ... B of LDS")."""
     assert K.get_option("ATTN_STREAM") == -1
+    B, n, H, hd = shape
+    # (1, 1153, 1, 32): the resident forward (16 waves) still holds it, the backward streams
+    assert A.path(BF, n, H, hd, False, B=B) == (A.FWD16 if shape == (1, 1153, 1, 32) else A.STREAM)
+    assert A.path(BF, n, H, hd, True, B=B) == A.STREAM
     o, lse = _fwd(dev, shape)
     _check_fwd(shape, o)
     dqkv, part = _bwd(dev, shape, o, lse)
@@ -119,9 +124,12 @@ def test_long_sequences_run_by_default(dev, shape):
 
 @pytest.mark.parametrize("shape", SMALL)
 def test_forced_at_small_shapes(dev, shape, opts):
+    B, n, H, hd = shape
     opts(ATTN_STREAM=0)
+    assert A.path(BF, n, H, hd, False, B=B) == A.FWD   # every SMALL shape: the 8-wave resident forward
     _, lse_r = _fwd(dev, shape)
     opts(ATTN_STREAM=1)
+    assert A.path(BF, n, H, hd, False, B=B) == A.path(BF, n, H, hd, True, B=B) == A.STREAM
     o, lse = _fwd(dev, shape)
     _check_fwd(shape, o)
     dqkv, part = _bwd(dev, shape, o, lse)
@@ -137,14 +145,17 @@ def test_streamed_and_resident_interchange(dev, opts):
     shape = (1, 197, 2, 64)
     for f, b in ((1, 0), (0, 1)):
         opts(ATTN_STREAM=f)
+        assert A.path(BF, 197, 2, 64, False) == (A.STREAM if f else A.FWD)
         o, lse = _fwd(dev, shape)
         _check_fwd(shape, o)
         opts(ATTN_STREAM=b)
+        assert A.path(BF, 197, 2, 64, True) == (A.STREAM if b else A.BWD_DIAG)
         _check_bwd(shape, *_bwd(dev, shape, o, lse))
 
 
 def test_deterministic(dev):
     shape = (2, 577, 2, 64)
+    assert A.path(BF, 577, 2, 64, False, B=2) == A.path(BF, 577, 2, 64, True, B=2) == A.STREAM
     runs = []
     for _ in range(2):
         o, lse = _fwd(dev, shape)
@@ -158,8 +169,12 @@ def test_deterministic(dev):
 def test_no_change_below_the_limit(dev, shape, opts):
     """an unset option routes every shape that ran before exactly as ATTN_STREAM = 0"""
     runs = []
+    B, n, H, hd = shape
+    # hd 64, n = 197: 8-wave forward, diagonal backward; hd 32, n = 577: the 16-wave forward and backward
+    want = (A.FWD, A.BWD_DIAG) if hd == 64 else (A.FWD16, A.BWD_16)
     for v in (None, 0):
         opts(ATTN_STREAM=v)
+        assert (A.path(BF, n, H, hd, False, B=B), A.path(BF, n, H, hd, True, B=B)) == want
         o, lse = _fwd(dev, shape)
         dqkv, part = _bwd(dev, shape, o, lse)
         runs.append((o, lse, dqkv, part))
@@ -187,6 +202,7 @@ def test_fp8_blocks_copy(dev, fmt):
     B, n, H, hd = shape
     D = H * hd
     q8 = K.new_fp8_blocks(B * n, D, fmt, dev)
+    assert A.path(BF, n, H, hd, False, q8=True) == A.path(BF, n, H, hd, True, q8=True) == A.STREAM
     o, lse = _fwd(dev, shape, q8=q8)
     r = K.quant_blocks_fp8(o, fmt)
     assert torch.equal(q8.q, r.q)
@@ -218,6 +234,9 @@ def test_vitl14_336_unmasked_model(dev):
     ref.eval()
     batch = make_batch(2, 336)
     bd = {k: v.to(dev) for k, v in batch.items()}
+    # the encoder's attention, 16 heads of 64 at n = 577: streamed in bf16, the rows kernels in fp32
+    for dt, want in ((BF, A.STREAM), (torch.float32, A.ROWS)):
+        assert A.path(dt, 577, 16, 64, False, B=2) == A.path(dt, 577, 16, 64, True, B=2) == want
     loss = prod(bd)
     loss.backward()
     p32(bd).backward()
@@ -259,6 +278,7 @@ def test_captured_block_replays_bitwise(dev):
     cache.refresh(BF)
     x0 = torch.randn(1, 577, 128, device=dev)
     gy = torch.randn(1, 577, 128, device=dev)
+    assert A.path(BF, 577, 2, 64, False) == A.path(BF, 577, 2, 64, True) == A.STREAM   # 2 heads of 64
 
     def step():
         for p in blocks.parameters():

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from mae_clip_amd import kernels as K
+from tests import attn_cases as A
 
 pytestmark = pytest.mark.gpu
 
@@ -271,6 +272,10 @@ def test_attention_fwd_bwd(dev, dtype, shape, mode, opts):
         pytest.skip("16-wave backward: bf16 with more than 8 16-row tiles")
     opts(ATTN_BW16=1 if mode == "bw16" else 0)
     opts(ATTN_TWO={"two": 1, "two3": 3}.get(mode, 0))
+    # the kernels this case runs, before it runs them: the mode's own, or the one the table names
+    # where a mode does not reach it ("two3" at hd 64 is the two-image kernel)
+    want = A.fwd_bwd_paths("bf16" if dtype == torch.bfloat16 else "f32", mode, shape)
+    assert (A.path(dtype, n, H, hd, False, B=B), A.path(dtype, n, H, hd, True, B=B)) == want
     scale = hd ** -0.5
     qkv = _rand((B * n, 3 * H * hd), dtype, dev, seed=11)
     o, lse = K.attn_fwd(qkv, B, n, H, hd, scale)
@@ -303,6 +308,7 @@ def test_attention_key_mask(dev):
     km = torch.ones((B, n), device=dev)
     km[1, 10:] = 0
     km[2, 3:] = 0
+    assert A.path(torch.bfloat16, n, H, hd, False, B=B, key_mask=True) == A.FWD
     o, _ = K.attn_fwd(qkv, B, n, H, hd, hd ** -0.5, key_mask=km)
     ref = _attn_ref(qkv, B, n, H, hd, hd ** -0.5, key_mask=km)
     assert (o.double() - ref).abs().max().item() < 2e-2
@@ -318,6 +324,8 @@ def test_attention_key_mask_f32(dev, rows, opts):
     km = torch.ones((B, n), device=dev)
     km[1, 10:] = 0
     km[2, 65:] = 0
+    for bwd in (False, True) if rows else (False,):
+        assert A.path(torch.float32, n, H, hd, bwd, B=B, key_mask=True) == (A.ROWS if rows else A.FWD)
     o, lse = K.attn_fwd(qkv, B, n, H, hd, hd ** -0.5, key_mask=km)
     ref = _attn_ref(qkv, B, n, H, hd, hd ** -0.5, key_mask=km)
     assert (o.double() - ref).abs().max().item() < 2e-5

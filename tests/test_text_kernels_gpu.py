@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from mae_clip_amd import kernels as K
+from tests import attn_cases as A
 
 pytestmark = pytest.mark.gpu
 
@@ -83,6 +84,7 @@ def test_attention_bwd_key_mask(dev, dtype, shape, lens):
     assert (o.double() - ref).abs().max().item() < tolf
     (ref * dout.double()).sum().backward()
     g = x64.grad
+    assert A.path(dtype, n, H, hd, True, B=B, key_mask=True) == A.BWD_MASKED
     dqkv, part = _bwd_guarded(qkv, o, dout, lse, B, n, H, hd, key_mask=km)
     _check_grads(dqkv, part, g, B, n, H, hd, tolb)
     # masked keys: dk / dv rows exactly zero, as in the reference
@@ -142,6 +144,7 @@ def test_attention_bwd_dropout(dev, dtype, masked, p, shape, lens):
     assert ferr < tolf / (1 - p)   # the kept probabilities, and with them O and its rounding, scale by 1/(1-p)
     (ref * dout.double()).sum().backward()
     kw = dict(key_mask=km, dropout_p=p, seed=seed, step_ptr=step)
+    assert A.path(dtype, n, H, hd, True, B=B, key_mask=masked, dropout_p=p) == A.BWD_MASKED
     dqkv, part = _bwd_guarded(qkv, o, dout, lse, B, n, H, hd, **kw)
     _check_grads(dqkv, part, x64.grad, B, n, H, hd, tolb)
     dq2, part2 = K.attn_bwd(qkv, o, dout, lse, B, n, H, hd, scale, **kw)
