@@ -215,6 +215,21 @@ int64_t maeclip_gemm_workspace(const maeclip_gemm_args* args);
  * launches nothing); nothing is launched and no device is needed. MAECLIP_GEMM_VARIANT (1..7 a v2 tile, 8 = v4 then v2,
  * 99 = v1) moves the answer as it moves the launch. */
 int32_t maeclip_gemm_impl(const maeclip_gemm_args* args);
+/* maeclip_gemm_impl plus, for a v4 call, its launch plan on `ncu` compute units
+ * (ncu <= 0: the current device's, the only case that needs a device):
+ * out = {tile height 256 / 192 / 128, in-launch split S (0: none), K-tiles of
+ * slice 0, grid x, y, z, dynamic LDS bytes, persistent (1: one block per CU
+ * loops over the tiles)}, zeros on the other routes; *workspace_bytes (may be
+ * NULL): maeclip_gemm_workspace of the call for ncu compute units (the v4
+ * split plan's scratch were a workspace offered, or the small path's K-slice
+ * partials). The plan options
+ * (maeclip_set_option) move the answer as they move the launch. Launches
+ * nothing. maeclip_gemm_fp8_plan: the same for maeclip_gemm_fp8 (blocks = 0) /
+ * maeclip_gemm_fp8_blocks (blocks != 0) after their argument checks; returns
+ * 4 or -1. */
+int32_t maeclip_gemm_plan(const maeclip_gemm_args* args, int32_t ncu, int32_t out[8], int64_t* workspace_bytes);
+int32_t maeclip_gemm_fp8_plan(const maeclip_gemm_args* args, int32_t blocks, int32_t ncu, int32_t out[8],
+                              int64_t* workspace_bytes);
 int32_t maeclip_gemm_splitk(int64_t M, int64_t N, int64_t K);
 
 /* Grouped weight gradients. Replaces the weight-gradient half of autograd's
@@ -239,6 +254,16 @@ int64_t maeclip_wgrad_grouped_workspace(const maeclip_wgrad_problem* probs, int3
                                         int32_t dtype);
 int32_t maeclip_wgrad_grouped(const maeclip_wgrad_problem* probs, int32_t nprob, int64_t M, int32_t dtype,
                               float beta, void* workspace, int64_t ws_bytes, void* stream);
+/* The launch plan of the first chunk (at most 48 problems) of such a call on
+ * `ncu` compute units (ncu <= 0: the current device's), without a launch:
+ * returns 1 and out = {output tiles T, uniform split-K slices S (1: none),
+ * stream-K remainder K-tiles per block skw (0: none), whole tiles Tdp and
+ * K-tiles per tile NT (both 0 without a remainder), blocks of the main launch,
+ * reduce launch (0 none, 1 split-K slabs, 2 stream-K remainder), its grid x, y,
+ * workspace bytes}; 0 when the list runs as one maeclip_gemm per problem; -1
+ * for a bad list. */
+int32_t maeclip_wgrad_grouped_plan(const maeclip_wgrad_problem* probs, int32_t nprob, int64_t M, int32_t dtype,
+                                   int32_t ncu, int64_t out[10]);
 
 /* ------------------------------------------------------------- attention
  * Replaces F.scaled_dot_product_attention in timm Attention / HF ViTMAE

@@ -278,6 +278,10 @@ _SIGS = {
     "maeclip_copy_f32": (c_i32, [c_vp, c_vp, C.c_int64, c_vp]),
     "maeclip_copy_f32_slot": (c_i32, [c_vp, c_vp, C.c_int64, c_vp, c_vp]),
     "maeclip_gemm_impl": (c_i32, [C.POINTER(GemmArgs)]),
+    "maeclip_gemm_plan": (c_i32, [C.POINTER(GemmArgs), c_i32, C.POINTER(c_i32 * 8), C.POINTER(c_i64)]),
+    "maeclip_gemm_fp8_plan": (c_i32, [C.POINTER(GemmArgs), c_i32, c_i32, C.POINTER(c_i32 * 8), C.POINTER(c_i64)]),
+    "maeclip_wgrad_grouped_plan": (c_i32, [C.POINTER(WgradProblem), c_i32, c_i64, c_i32, c_i32,
+                                           C.POINTER(c_i64 * 10)]),
     "maeclip_scale_by_scalar2": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, C.c_float, c_vp]),
     "maeclip_memcpy_h2d": (c_i32, [c_vp, c_vp, c_sz, c_vp]),
     "maeclip_timestamp": (c_i32, [c_vp, c_vp]),

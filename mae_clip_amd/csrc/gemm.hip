@@ -30,7 +30,7 @@
 // This file also holds the public entry: the argument checks, the routing of a
 // call to one of the four kernel families (maeclip::gemm_route) and the
 // split-K reduction that v1, v2 and v4 share.
-#include "gemm_common.h"
+#include "gemm4_plan.h"
 #include <stdlib.h>
 
 namespace {
@@ -364,6 +364,31 @@ extern "C" int32_t maeclip_gemm_impl(const maeclip_gemm_args* a) {
   bool empty;
   if (int e = check_args(a, "maeclip_gemm_impl", &empty)) return e;
   return empty ? 0 : (int32_t)maeclip::gemm_route(*a);
+}
+
+// The route as maeclip_gemm_impl returns it and, for a v4 call, its launch plan
+// on ncu CUs (ncu <= 0: this device's, the only case that touches HIP): out =
+// {tile height, in-launch split S (0: none), slice 0's K-tiles, grid x, y, z,
+// LDS bytes, persistent}, zeros on the other routes; *workspace_bytes
+// (optional) = maeclip_gemm_workspace for ncu CUs: what the v4 plan would use
+// were a workspace offered, or the small path's K-slice partials.
+extern "C" int32_t maeclip_gemm_plan(const maeclip_gemm_args* a, int32_t ncu, int32_t out[8],
+                                     int64_t* workspace_bytes) {
+  bool empty;
+  if (int e = check_args(a, "maeclip_gemm_plan", &empty)) return e;
+  MC_CHECK_ARG(out != nullptr, "maeclip_gemm_plan: null out");
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  if (workspace_bytes) *workspace_bytes = 0;
+  if (empty) return 0;
+  const maeclip::GemmRoute route = maeclip::gemm_route(*a);
+  if (route == maeclip::GemmRoute::V4) {
+    if (ncu <= 0) ncu = maeclip::gemm4_device_ncu();
+    maeclip::gemm4_plan_out(maeclip::gemm4_plan(*a, maeclip::G4_BF16, ncu, a->workspace != nullptr), out);
+    if (workspace_bytes) *workspace_bytes = maeclip::gemm4_plan(*a, maeclip::G4_BF16, ncu, true).workspace_bytes;
+  } else if (route == maeclip::GemmRoute::SMALL && workspace_bytes && a->splitk <= 1) {
+    *workspace_bytes = maeclip::gemm_small_workspace(*a);
+  }
+  return (int32_t)route;
 }
 
 // Scratch bytes maeclip_gemm may use for this call when the caller asks for no

@@ -1,10 +1,10 @@
-// What the four GEMM files (gemm.hip v1, gemm2.hip v2, gemm4.hip v4 + fp8,
-// gemm_small.hip) share, stated once: the layout and epilogue values of
+// What the GEMM files (gemm.hip v1, gemm2.hip v2, gemm4*.hip v4 / fp8 / grouped
+// weight gradients, gemm_small.hip) share, stated once: the layout and epilogue values of
 // maeclip_gemm_args, the host dispatch from those runtime values to template
 // arguments, the declarations of what one file calls in another, and the
 // fragment reader and fragment epilogue of the two 16x16-fragment kernels that
 // keep one output row x 4 columns per lane (v1 and v2). Internal: included by
-// those four files only.
+// those files only.
 #pragma once
 #include "common.h"
 #include "../../include/maeclip.h"
@@ -30,7 +30,7 @@ int gemm_v2(const maeclip_gemm_args& a, hipStream_t s, int variant);  // gemm2.h
 int gemm_v4(const maeclip_gemm_args& a, hipStream_t s);               // gemm4.hip
 bool gemm_v4_ok(const maeclip_gemm_args& a);
 int64_t gemm_v4_workspace(const maeclip_gemm_args& a);
-int check_q8(const maeclip_gemm_args& a, const char* who);
+int check_q8(const maeclip_gemm_args& a, const char* who);        // gemm4_fp8.hip
 int gemm_small(const maeclip_gemm_args& a, hipStream_t s);            // gemm_small.hip
 bool gemm_small_ok(const maeclip_gemm_args& a);
 int64_t gemm_small_workspace(const maeclip_gemm_args& a);

@@ -365,6 +365,41 @@ def linear_fp8(xq, wq: Fp8Rows, bias=None, out_dtype=torch.bfloat16, epilogue=EP
                     q8=q8)
 
 
+def gemm_plan(a, ncu=0, fp8=None):
+    """The launch plan of the GEMM call described by the L.GemmArgs `a` on `ncu`
+    compute units (0: this device's), without a launch (maeclip_gemm_plan; fp8 =
+    "rows" / "blocks": maeclip_gemm_fp8_plan): dict of route (maeclip_gemm_impl's
+    number) and, for a v4 route, bm, S (in-launch split, 0 = none), L0, grid,
+    lds_bytes, persistent, workspace_bytes (what maeclip_gemm_workspace asks for)."""
+    out, ws = (C.c_int32 * 8)(), C.c_int64(0)
+    if fp8 is None:
+        route = L.lib().maeclip_gemm_plan(C.byref(a), int(ncu), C.byref(out), C.byref(ws))
+    else:
+        route = L.lib().maeclip_gemm_fp8_plan(C.byref(a), int(fp8 == "blocks"), int(ncu), C.byref(out), C.byref(ws))
+    if route < 0:
+        L.check(route, "maeclip_gemm_plan")
+    bm, S, L0, gx, gy, gz, lds, pers = out
+    return dict(route=int(route), bm=bm, S=S, L0=L0, grid=(gx, gy, gz), lds_bytes=lds, persistent=bool(pers),
+                workspace_bytes=int(ws.value))
+
+
+def wgrad_plan(probs, n, M, dtype=L.BF16, ncu=0):
+    """The launch plan of the first chunk of a maeclip_wgrad_grouped call on the
+    L.WgradProblem array `probs` (maeclip_wgrad_grouped_plan), or None when the
+    list runs as one GEMM per problem: dict of T, S, skw, Tdp, NT, grid, reduce,
+    reduce_grid, workspace_bytes and mode ("streamk" remainder, "split" uniform
+    slices, "whole" tiles only)."""
+    out = (C.c_int64 * 10)()
+    rc = L.lib().maeclip_wgrad_grouped_plan(probs, int(n), int(M), int(dtype), int(ncu), C.byref(out))
+    if rc < 0:
+        L.check(rc, "maeclip_wgrad_grouped_plan")
+    if rc == 0:
+        return None
+    T, S, skw, Tdp, NT, grid, red, rgx, rgy, ws = (int(v) for v in out)
+    return dict(T=T, S=S, skw=skw, Tdp=Tdp, NT=NT, grid=grid, reduce=red, reduce_grid=(rgx, rgy), workspace_bytes=ws,
+                mode="streamk" if skw > 0 else "split" if S > 1 else "whole")
+
+
 def gemm_colsum_rows(M: int) -> int:
     return int(L.lib().maeclip_gemm_colsum_rows(M))
 

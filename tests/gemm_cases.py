@@ -450,3 +450,201 @@ def v4_split_cases():
     o = (("GEMM_SPLIT", 2), ("GEMM_BM", 192))
     return [legal(Case("v4", 264, 264, 256, KC, lb, BF16, out, opts=o, plan_ws=True, seed=90 + lb, tag="split2"))
             for lb in (KC, RC) for out in (F32, BF16)]
+
+
+# ---------------------------------------------------------- v4 launch plans
+# Labelled by hand from the rules in mae_clip_amd/csrc/gemm4_plan.h (gemm4_plan, wgrad_plan), at 256 and at 64 CUs.
+# Cost model of a plain launch, in 256-row K-tiles: rounds of the grid x (K-tiles x c + 2.5), c = 1 (256 rows),
+# 0.89 (192), 0.72 (128); a split of S = 2 on 192-row tiles costs rounds x L0 x 0.89 + 2.5 + 2.
+PLAN_OPTS = ("GEMM_BM", "GEMM_SK", "GEMM_SPLIT", "GEMM_SPLIT_D", "GEMM_SPLIT_MINK", "GEMM_BM128", "GEMM_GRID", "WG_SK")
+LDS = {256: 163840, 192: 149504, 128: 131072}     # 2 operand stages (+ 2 KiB of fp8 scale images at 192) + 32 KiB
+
+
+def sk_ws(ncu):
+    """16 KiB of arrival counters + two fp32 256 x 256 partial tiles per CU"""
+    return 16384 + 2 * ncu * 262144
+
+
+@dataclasses.dataclass
+class PlanCase:
+    tag: str
+    M: int
+    N: int
+    K: int
+    want: dict                # ncu -> (bm, S, L0, (grid x, y, z), persistent)
+    family: str = "bf16"      # bf16 / fp8rows / fp8blocks
+    la: int = KC
+    colsum: bool = False
+    batch: int = 1
+    S: int = 1                # caller's split-K
+    ws: bool = False          # a workspace is offered
+    opts: tuple = ()
+
+    @property
+    def id(self):
+        return self.tag
+
+
+def plan_args(c):
+    from mae_clip_amd import _lib as L
+    f8 = c.family != "bf16"
+    return L.GemmArgs(A=4096, B=4096, C=4096, M=c.M, N=c.N, K=c.K, lda=c.K if c.la == KC else c.M, ldb=c.K, ldc=c.N,
+                      batch=c.batch, strideA=c.M * c.K, strideB=c.N * c.K, strideC=c.M * c.N,
+                      dtype=2 if f8 else L.BF16, out_dtype=L.F32, a_layout=c.la, b_layout=KC, epilogue=0, alpha=1.0,
+                      beta=0.0, colsum_partial=4096 if c.colsum else None, splitk=c.S,
+                      workspace=4096 if (c.ws or c.S > 1) else None)
+
+
+def plan_cases():
+    P = PlanCase
+    split = (("GEMM_SPLIT", 2), ("GEMM_BM", 192))
+    cs = [
+        # encoder N = 768: 256 rows 50 x 3 = 150 tiles, 192 rows 67 x 3 = 201. 256 CUs: one round each, 12 + 2.5 =
+        # 14.5 against 12 x 0.89 + 2.5 = 13.18 -> 192. 64 CUs: 3 rounds x 14.5 = 43.5 against 4 x 13.18 = 52.7 -> 256
+        P("enc768", 12800, 768, 768, {256: (192, 0, 0, (201, 1, 1), True), 64: (256, 0, 0, (64, 1, 1), True)}),
+        # 64 x 4 = 256 tiles of 256 rows: one full round (4 + 2.5 = 6.5); 192 rows: 86 x 4 = 344 tiles = 2 rounds
+        # (2 x 6.06). 64 CUs: 4 rounds x 6.5 = 26 against 6 x 6.06 = 36.4
+        P("full_round", 16384, 1024, 256, {256: (256, 0, 0, (256, 1, 1), True), 64: (256, 0, 0, (64, 1, 1), True)}),
+        # row-contiguous A / column sums: 256 rows only
+        P("rc_a", 12800, 768, 768, {256: (256, 0, 0, (150, 1, 1), True), 64: (256, 0, 0, (64, 1, 1), True)}, la=RC),
+        P("colsum", 12800, 768, 768, {256: (256, 0, 0, (150, 1, 1), True), 64: (256, 0, 0, (64, 1, 1), True)},
+          colsum=True),
+        # caller split-K / batched: 256 rows, one block per (tile, slice, batch); 2 x 2 and 50 x 3 tiles
+        P("caller_splitk", 264, 264, 128, {256: (256, 0, 0, (4, 3, 1), False), 64: (256, 0, 0, (4, 3, 1), False)}, S=3),
+        P("batched", 264, 264, 128, {256: (256, 0, 0, (4, 1, 3), False), 64: (256, 0, 0, (4, 1, 3), False)}, batch=3),
+        P("batched_big", 12800, 768, 768, {256: (256, 0, 0, (150, 1, 2), False), 64: (256, 0, 0, (150, 1, 2), False)},
+          batch=2),
+        P("splitk_batched", 264, 264, 128, {256: (256, 0, 0, (4, 4, 2), False), 64: (256, 0, 0, (4, 4, 2), False)},
+          S=4, batch=2, opts=(("GEMM_BM", 192),)),
+        # forced tile heights: 100 x 3 = 300, 201, 150 tiles
+        P("bm128", 12800, 768, 768, {256: (128, 0, 0, (256, 1, 1), True), 64: (128, 0, 0, (64, 1, 1), True)},
+          opts=(("GEMM_BM", 128),)),
+        P("bm192", 12800, 768, 768, {256: (192, 0, 0, (201, 1, 1), True), 64: (192, 0, 0, (64, 1, 1), True)},
+          opts=(("GEMM_BM", 192),)),
+        P("bm256", 12800, 768, 768, {256: (256, 0, 0, (150, 1, 1), True), 64: (256, 0, 0, (64, 1, 1), True)},
+          opts=(("GEMM_BM", 256),)),
+        # a forced height the launch cannot take (row-contiguous A) falls back to 256
+        P("bm192_rc_a", 12800, 768, 768, {256: (256, 0, 0, (150, 1, 1), True), 64: (256, 0, 0, (64, 1, 1), True)},
+          la=RC, opts=(("GEMM_BM", 192),)),
+        # forced split of 2 on 192-row tiles, 2 x 2 tiles, K = 256: NT = 4 = 2 S fits; the whole grid launches.
+        # lead 4: L0 = ceil((4 + 4) / 2) = 4, capped at NT - 1 = 3; lead 0: L0 = 2
+        P("split2_k256", 264, 264, 256, {256: (192, 2, 3, (256, 1, 1), True), 64: (192, 2, 3, (64, 1, 1), True)},
+          ws=True, opts=split),
+        P("split2_k256_lead0", 264, 264, 256, {256: (192, 2, 2, (256, 1, 1), True), 64: (192, 2, 2, (64, 1, 1), True)},
+          ws=True, opts=split + (("GEMM_SPLIT_D", 0),)),
+        # K = 1024, NT = 16: lead 4 -> ceil(20 / 2) = 10, lead 9 -> ceil(25 / 2) = 13
+        P("split2_k1024", 264, 264, 1024, {256: (192, 2, 10, (256, 1, 1), True), 64: (192, 2, 10, (64, 1, 1), True)},
+          ws=True, opts=split),
+        P("split2_k1024_lead9", 264, 264, 1024, {256: (192, 2, 13, (256, 1, 1), True), 64: (192, 2, 13, (64, 1, 1), True)},
+          ws=True, opts=split + (("GEMM_SPLIT_D", 9),)),
+        # K = 192: NT = 3 < 2 S does not fit -> the best data-parallel plan (192 rows forced, 4 tiles)
+        P("split2_k192", 264, 264, 192, {256: (192, 0, 0, (4, 1, 1), True), 64: (192, 0, 0, (4, 1, 1), True)},
+          ws=True, opts=split),
+        # no workspace offered: no split
+        P("split2_no_ws", 264, 264, 256, {256: (192, 0, 0, (4, 1, 1), True), 64: (192, 0, 0, (4, 1, 1), True)},
+          opts=split),
+        # the cost model's split (GEMM_SK = 1): 6400 x 768 x 3072, NT = 48; 256 rows 75 tiles (50.5), 192 rows 102
+        # tiles (48 x 0.89 + 2.5 = 45.2); split of the 102: 204 units = one round of 256, L0 = ceil(52 / 2) = 26:
+        # 26 x 0.89 + 4.5 = 27.6 -> taken. 64 CUs: 204 units > 2 x 64 -> none; 2 rounds x 45.2 against 2 x 50.5 -> 192
+        P("sk_ws", 6400, 768, 3072, {256: (192, 2, 26, (256, 1, 1), True), 64: (192, 0, 0, (64, 1, 1), True)},
+          ws=True, opts=(("GEMM_SK", 1),)),
+        P("sk_no_ws", 6400, 768, 3072, {256: (192, 0, 0, (102, 1, 1), True), 64: (192, 0, 0, (64, 1, 1), True)},
+          opts=(("GEMM_SK", 1),)),
+        # without GEMM_SK a workspace changes nothing
+        P("ws_default", 6400, 768, 3072, {256: (192, 0, 0, (102, 1, 1), True), 64: (192, 0, 0, (64, 1, 1), True)},
+          ws=True),
+        # fp8 rows, K-tile 128: 9280 x 1024 x 512 is NT = 4; 256 rows 37 x 4 = 148 tiles (6.5), 192 rows 49 x 4 = 196
+        # (4 x 0.89 + 2.5 = 6.06) -> 192; 64 CUs: 3 x 6.5 against 4 x 6.06 -> 256
+        P("fp8_rows", 9280, 1024, 512, {256: (192, 0, 0, (196, 1, 1), True), 64: (256, 0, 0, (64, 1, 1), True)},
+          family="fp8rows"),
+        # the forced split needs 4 K-tiles of 128: not at K = 256 (bf16 fits there), at K = 512 with L0 = 3
+        P("fp8_rows_split_k256", 264, 264, 256, {256: (192, 0, 0, (4, 1, 1), True), 64: (192, 0, 0, (4, 1, 1), True)},
+          family="fp8rows", ws=True, opts=split),
+        P("fp8_rows_split_k512", 264, 264, 512, {256: (192, 2, 3, (256, 1, 1), True), 64: (192, 2, 3, (64, 1, 1), True)},
+          family="fp8rows", ws=True, opts=split),
+        # a forced 128 rules 192 out, and 128-row tiles are bf16 only: fp8 is left with 256 rows (148 tiles)
+        P("fp8_rows_bm128", 9280, 1024, 512, {256: (256, 0, 0, (148, 1, 1), True), 64: (256, 0, 0, (64, 1, 1), True)},
+          family="fp8rows", opts=(("GEMM_BM", 128),)),
+        P("fp8_rows_batched", 264, 264, 512, {256: (256, 0, 0, (4, 1, 2), False), 64: (256, 0, 0, (4, 1, 2), False)},
+          family="fp8rows", batch=2),
+        # fp8 blocks: always 192 rows, never a split
+        P("fp8_blocks", 9280, 1024, 512, {256: (192, 0, 0, (196, 1, 1), True), 64: (192, 0, 0, (64, 1, 1), True)},
+          family="fp8blocks"),
+        P("fp8_blocks_forced", 264, 264, 512, {256: (192, 0, 0, (4, 1, 1), True), 64: (192, 0, 0, (4, 1, 1), True)},
+          family="fp8blocks", ws=True, opts=(("GEMM_SPLIT", 2), ("GEMM_BM", 256), ("GEMM_SK", 1))),
+    ]
+    return cs
+
+
+@dataclasses.dataclass
+class WgradCase:
+    tag: str
+    shapes: list              # (N, K) of every problem
+    M: int
+    want: dict                # ncu -> dict of the plan fields that are checked
+    opts: tuple = ()
+
+    @property
+    def id(self):
+        return self.tag
+
+
+ENC_LAYER = [(2304, 768), (768, 768), (3072, 768), (768, 3072)]     # 27 + 9 + 36 + 36 = 108 tiles of 256 x 256
+DEC_LAYER = [(1536, 512), (512, 512), (2048, 512), (512, 2048)]     # 12 + 4 + 16 + 16 = 48 tiles
+
+
+def wgrad_problems(shapes):
+    from mae_clip_amd import _lib as L
+    probs = (L.WgradProblem * len(shapes))()
+    for q, (N, K) in zip(probs, shapes):
+        q.dy, q.x, q.dw, q.N, q.K, q.ldy, q.ldx = 4096, 4096, 4096, N, K, N, K
+    return probs
+
+
+def wgrad_plan_cases():
+    W = WgradCase
+    sk = lambda ncu: 2 * ncu * 262144          # two fp32 256 x 256 slots per block
+    dec_nk = 8 * sum(n * k for n, k in DEC_LAYER)
+    return [
+        # encoder: 12 x 108 = 1296 tiles, NT = 12800 / 64 = 200. 256 CUs: remainder 1296 % 256 = 16 tiles,
+        # skw = ceil(16 x 200 / 256) = 13 >= 8, Tdp = 1280. 64 CUs: 1296 % 64 = 16, skw = ceil(3200 / 64) = 50
+        W("encoder48", ENC_LAYER * 12, 12800,
+          {256: dict(mode="streamk", T=1296, S=1, skw=13, Tdp=1280, NT=200, grid=256, reduce=2, reduce_grid=(16, 16),
+                     workspace_bytes=sk(256)),
+           64: dict(mode="streamk", T=1296, S=1, skw=50, Tdp=1280, NT=200, grid=64, reduce=2, reduce_grid=(16, 16),
+                    workspace_bytes=sk(64))}),
+        # decoder: 8 x 48 = 384 tiles, NT = 50432 / 64 = 788. 256 CUs: remainder 128 tiles, skw = ceil(128 x 788 /
+        # 256) = 394, Tdp = 256. 64 CUs: 384 = 6 rounds, no remainder; slices: S = 2, 3, 4 all keep 6 rounds per
+        # tile-K (12 / 2, 18 / 3, 24 / 4), none beats 6 by 15 % -> whole tiles
+        W("decoder32", DEC_LAYER * 8, 50432,
+          {256: dict(mode="streamk", T=384, S=1, skw=394, Tdp=256, NT=788, grid=256, reduce=2, reduce_grid=(128, 16),
+                     workspace_bytes=sk(256)),
+           64: dict(mode="whole", T=384, S=1, skw=0, Tdp=0, NT=0, grid=64, reduce=0, workspace_bytes=0)}),
+        # WG_SK = 0, decoder. 256 CUs: S = 1 costs ceil(384 / 256) = 2 rounds; S = 2: ceil(768 / 256) / 2 = 1.5 <
+        # 0.85 x 2; S = 3: 5 / 3 and S = 4: 6 / 4 do not beat 1.5 -> S = 2: two fp32 slabs of every dW; the reduce
+        # covers the largest dW (2048 x 512 / 4 / 256 = 1024 blocks) x 32 problems
+        W("decoder32_uniform", DEC_LAYER * 8, 50432,
+          {256: dict(mode="split", T=384, S=2, skw=0, grid=256, reduce=1, reduce_grid=(1024, 32),
+                     workspace_bytes=2 * dec_nk * 4),
+           64: dict(mode="whole", T=384, S=1, skw=0, grid=64, reduce=0, workspace_bytes=0)}, opts=(("WG_SK", 0),)),
+        # WG_SK = 0, encoder: 6 rounds; S = 2: 11 / 2, S = 3: 16 / 3, S = 4: 21 / 4 are all above 0.85 x 6 = 5.1.
+        # 64 CUs: 21 rounds; 41 / 2, 61 / 3, 81 / 4 are all above 17.85
+        W("encoder48_uniform", ENC_LAYER * 12, 12800,
+          {256: dict(mode="whole", T=1296, S=1, skw=0, grid=256, reduce=0, workspace_bytes=0),
+           64: dict(mode="whole", T=1296, S=1, skw=0, grid=64, reduce=0, workspace_bytes=0)}, opts=(("WG_SK", 0),)),
+        # 16 x 16 = 256 tiles: a multiple of both grids, no remainder; slices never cut the rounds per tile-K
+        W("full_rounds", [(4096, 4096)], 4096,
+          {256: dict(mode="whole", T=256, S=1, skw=0, Tdp=0, grid=256, reduce=0, workspace_bytes=0),
+           64: dict(mode="whole", T=256, S=1, skw=0, Tdp=0, grid=64, reduce=0, workspace_bytes=0)}),
+        # 4 tiles, NT = 64: skw = ceil(4 x 64 / 256) = 1 < 8 -> no stream-K; S = 4 (16 K-tiles each) cuts the one
+        # round to 1 / 4. 64 CUs: skw = ceil(256 / 64) = 4 < 8, the same
+        W("few_tiles", [(512, 256), (256, 512)], 4096,
+          {256: dict(mode="split", T=4, S=4, skw=0, grid=16, reduce=1, reduce_grid=(128, 2),
+                     workspace_bytes=4 * 2 * 512 * 256 * 4),
+           64: dict(mode="split", T=4, S=4, skw=0, grid=16, reduce=1, reduce_grid=(128, 2),
+                    workspace_bytes=4 * 2 * 512 * 256 * 4)}),
+        # 52 problems: the plan is the first chunk's, the encoder's 48
+        W("longer_than_a_chunk", ENC_LAYER * 13, 12800,
+          {256: dict(mode="streamk", T=1296, S=1, skw=13, Tdp=1280, grid=256, reduce_grid=(16, 16)),
+           64: dict(mode="streamk", T=1296, S=1, skw=50, Tdp=1280, grid=64, reduce_grid=(16, 16))}),
+    ]

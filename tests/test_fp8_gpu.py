@@ -96,6 +96,16 @@ def _deq(op):
     return op.q.cpu().view(tdt).double() * op.s.cpu().double().view(-1, 1)
 
 
+def _fp8_plan(dev, M, N, Kd, blocks=False):
+    """K.gemm_plan of an fp8 launch of this shape (a workspace offered) under the current options with the
+    device's CU count"""
+    from mae_clip_amd import _lib as L
+    a = L.GemmArgs(A=16, B=16, C=16, M=M, N=N, K=Kd, lda=Kd, ldb=Kd, ldc=N, batch=1, dtype=K.FP8_E4M3,
+                   out_dtype=L.F32, a_layout=0, b_layout=0, alpha=1.0, splitk=1, workspace=None if blocks else 16)
+    return K.gemm_plan(a, torch.cuda.get_device_properties(dev).multi_processor_count,
+                       fp8="blocks" if blocks else "rows")
+
+
 @pytest.mark.parametrize("bm", ["auto", "192", "sk", "sk192"])
 @pytest.mark.parametrize("afmt", [K.FP8_E4M3, K.FP8_E5M2])
 @pytest.mark.parametrize("mnk", [(512, 384, 256), (1000, 768, 1024), (2308, 512, 2048), (9280, 1024, 512)])
@@ -109,6 +119,10 @@ def test_gemm_fp8_vs_dequantised_fp64(dev, afmt, mnk, bm, opts):
     if bm.startswith("sk"):   # stream-K forced wherever the tiles leave a partial last round
         opts(GEMM_SK=1)
     M, N, Kd = mnk
+    p = _fp8_plan(dev, M, N, Kd)
+    if bm in ("192", "sk192"):
+        assert p["bm"] == 192, p
+    assert p["S"] in ((0, 2) if bm.startswith("sk") else (0,)) and (p["S"] == 0 or p["bm"] == 192), p
     g = torch.Generator().manual_seed(M + N)
     x = (torch.randn(M, Kd, generator=g) * 3).to(torch.bfloat16).to(dev)
     w = (torch.randn(N, Kd, generator=g) * 0.05).to(dev)
@@ -208,6 +222,8 @@ def test_gemm_fp8_blocks_vs_dequantised_fp64(dev, afmt, mnk):
     (plain bf16, fp32 residual); A rows with blocks 2^30 apart in magnitude so
     a wrong scale byte cannot hide. (18560, 1024, 4096): the C4 encoder's fc2."""
     M, N, Kd = mnk
+    p = _fp8_plan(dev, M, N, Kd, blocks=True)
+    assert (p["bm"], p["S"]) == (192, 0), p
     g = torch.Generator().manual_seed(M + N + 1)
     x = torch.randn(M, Kd, generator=g) * 3
     x[:, : Kd // 2] *= 2.0 ** -15
@@ -245,6 +261,13 @@ def test_gemm_epilogue_fp8_blocks_output(dev, path, fmt, opts):
     aux = torch.rand(M, N, generator=g).to(torch.bfloat16).to(dev)
     if path == "bf16_192":
         opts(GEMM_BM=192)
+        from mae_clip_amd import _lib as L
+        a = L.GemmArgs(A=16, B=16, C=16, M=M, N=N, K=Kd, lda=Kd, ldb=Kd, ldc=N, batch=1, dtype=L.BF16,
+                       out_dtype=L.BF16, a_layout=0, b_layout=0, alpha=1.0, splitk=1)
+        p = K.gemm_plan(a, torch.cuda.get_device_properties(dev).multi_processor_count)
+        assert (p["route"], p["bm"], p["S"]) == (4, 192, 0), p
+    elif path == "fp8blocks":
+        assert _fp8_plan(dev, M, N, Kd, blocks=True)["bm"] == 192
     if path.startswith("bf16"):
         wb = w.to(torch.bfloat16)
 

@@ -48,6 +48,8 @@ def test_gemm_bm192(dev, b_lay, mnk, bm, opts):
     block (M = 50000: 261 x 2 tiles on 256 CUs at 192 rows), one K-tile, KC x KC and KC x RC."""
     opts(GEMM_BM=int(bm))
     M, N, Kd = mnk
+    p = _plan(dev, M, N, Kd, b_lay)     # M < 256 is below the v4 kernel: those shapes run on v2
+    assert p["route"] == (4 if M >= 256 else 2) and (M < 256 or (p["bm"], p["S"]) == (int(bm), 0)), p
     A = _rand((M, Kd), torch.bfloat16, dev, seed=1)
     B = _rand((N, Kd) if b_lay == 0 else (Kd, N), torch.bfloat16, dev, seed=2)
     for out in (torch.float32, torch.bfloat16):
@@ -71,6 +73,21 @@ def _plan_workspace(dev, M, N, Kd, b_lay):
     a = L.GemmArgs(A=16, B=16, C=16, M=M, N=N, K=Kd, lda=Kd, ldb=Kd if b_lay == 0 else N, ldc=N, batch=1,
                    dtype=L.BF16, out_dtype=L.F32, a_layout=0, b_layout=b_lay, alpha=1.0, splitk=1)
     return int(L.lib().maeclip_gemm_workspace(ctypes.byref(a)))
+
+
+def _plan(dev, M, N, Kd, b_lay, colsum=False):
+    """K.gemm_plan of this plain bf16 launch (fp32 out, K-contiguous A, a workspace offered) under the current
+    options with the device's CU count"""
+    from mae_clip_amd import _lib as L
+    a = L.GemmArgs(A=16, B=16, C=16, M=M, N=N, K=Kd, lda=Kd, ldb=Kd if b_lay == 0 else N, ldc=N, batch=1,
+                   dtype=L.BF16, out_dtype=L.F32, a_layout=0, b_layout=b_lay, alpha=1.0, splitk=1, workspace=16,
+                   colsum_partial=16 if colsum else None)
+    return K.gemm_plan(a, _ncu(dev))
+
+
+def _lead_l0(NT, lead):
+    """K-tiles of slice 0 of a split of 2: longer by `lead`, the other slice keeps at least one K-tile"""
+    return max(min(-(-(NT + lead) // 2), NT - 1), -(-NT // 2))
 
 
 def _sk_counters_zero():
@@ -111,6 +128,13 @@ def test_gemm_stream_k(dev, b_lay, mnk, mode, opts):
         T = -(-M // 192) * -(-N // 256)
         fits = T <= 256 and 2 * T <= 2 * _ncu(dev) and Kd // 64 >= 4
         assert (_plan_workspace(dev, M, N, Kd, b_lay) > 0) == fits, (mnk, T)
+        p = _plan(dev, M, N, Kd, b_lay)
+        lead = int(mode.split("_lead")[1]) if "_lead" in mode else 4
+        assert (p["bm"], p["S"], p["L0"]) == ((192, 2, _lead_l0(Kd // 64, lead)) if fits else (192, 0, 0)), p
+        assert p["grid"] == ((_ncu(dev) if fits else min(T, _ncu(dev))), 1, 1) and p["persistent"]
+    else:   # the cost model's choice: a split exactly where the workspace query asks for scratch
+        p = _plan(dev, M, N, Kd, b_lay)
+        assert (p["S"] > 0) == (_plan_workspace(dev, M, N, Kd, b_lay) > 0) and p["S"] in (0, 2), p
     A = _rand((M, Kd), torch.bfloat16, dev, seed=11)
     B = _rand((N, Kd) if b_lay == 0 else (Kd, N), torch.bfloat16, dev, scale=0.5, seed=12)
     ref = _ref_mm(A, B.t() if b_lay == 0 else B)
@@ -143,6 +167,10 @@ def test_gemm_stream_k_epilogues(dev, mode, opts):
     M, N, Kd = 3000, 768, 1024
     if mode != "bm128":   # 16 x 3 tiles: every tile is cut
         assert _plan_workspace(dev, M, N, Kd, 0) > 0
+    for n_, k_ in ((N, Kd), (Kd, N)):   # the forward launches and the dgrads
+        p = _plan(dev, M, n_, k_, 0)
+        assert (p["bm"], p["S"]) == ((128, 0) if mode == "bm128" else (192, 2)), p
+    assert _plan(dev, M, N, Kd, 0, colsum=True)["bm"] == 256   # column sums keep 256-row tiles
     x = _rand((M, Kd), torch.bfloat16, dev, seed=13)
     w = _rand((N, Kd), torch.bfloat16, dev, scale=0.03, seed=14)
     bias = _rand((N,), torch.float32, dev, seed=15)
@@ -189,6 +217,9 @@ def test_gemm_epilogues(dev, dtype, M, bm, opts):
             pytest.skip("192-row tiles: bf16 operands")
         opts(GEMM_BM=192)
     N, Kd = 384, 256
+    if bm != "auto" and M >= 256:
+        for n_, k_ in ((N, Kd), (Kd, N)):
+            assert (_plan(dev, M, n_, k_, 0)["bm"], _plan(dev, M, n_, k_, 0, colsum=True)["bm"]) == (192, 256)
     x = _rand((M, Kd), dtype, dev, seed=3)
     w = _rand((N, Kd), dtype, dev, scale=0.05, seed=4)
     bias = _rand((N,), torch.float32, dev, seed=5)
@@ -576,12 +607,21 @@ def test_wgrad_grouped(dev, case, opts):
         out = torch.empty((N, Kd), device=dev, dtype=torch.float32)
         items.append((dy, x, out))
         refs.append(_ref_mm(dy.t(), x))
+    probs = (_lib.WgradProblem * len(items))()
+    for q, (dy, x, out) in zip(probs, items):
+        q.dy, q.x, q.dw, q.N, q.K, q.ldy, q.ldx = dy.data_ptr(), x.data_ptr(), out.data_ptr(), dy.shape[1], \
+            x.shape[1], dy.stride(0), x.stride(0)
     if case == "few_tiles_splitk":
-        probs = (_lib.WgradProblem * 2)()
-        for q, (dy, x, out) in zip(probs, items):
-            q.dy, q.x, q.dw, q.N, q.K, q.ldy, q.ldx = dy.data_ptr(), x.data_ptr(), out.data_ptr(), dy.shape[1], \
-                x.shape[1], dy.stride(0), x.stride(0)
         assert _lib.lib().maeclip_wgrad_grouped_workspace(probs, 2, M, 1) > 0
+    # the plan on this device; the labels are wgrad_plan's rules (gemm4_plan.h) worked for 256 CUs: a remainder of
+    # 108 / 96 / 128 tiles at 50 / 100 / 32 K-tiles is 22 / 38 / 16 K-tiles per block (>= 8: stream-K); 96 tiles with
+    # WG_SK = 0 halve their one round with S = 2; 4 tiles leave 1 K-tile per block (< 8) and take S = 4 slices
+    p = K.wgrad_plan(probs, len(items), M, dtype=_lib.F32 if dt == torch.float32 else _lib.BF16, ncu=_ncu(dev))
+    want = {"encoder4": ("streamk", 22, 1), "strided": ("streamk", 22, 1), "decoder2x4": ("streamk", 38, 1),
+            "whole_plus_streamk": ("streamk", 16, 1), "uniform_slices": ("split", 0, 2),
+            "few_tiles_splitk": ("split", 0, 4), "fp32_fallback": None}[case]
+    if _ncu(dev) == 256 or want is None:
+        assert (p and (p["mode"], p["skw"], p["S"])) == want, p
     K.wgrad_grouped(items)
     for (dy, x, out), ref in zip(items, refs):
         assert (out.double() - ref).abs().max().item() / ref.abs().max().item() < 1e-5

@@ -48,7 +48,7 @@ def kernels(objs, match):
                 if m:
                     cur = m.group(1)
                     text[cur] = []
-                elif cur and line.strip():
+                elif cur and line.strip() and line.strip() != "...":   # "...": zero fill after a section's last kernel
                     text[cur].append(re.sub(r"\s*//.*$", "", line).strip())
             for name, row in rows.items():
                 if match in name:
@@ -76,8 +76,10 @@ def main():
         same_row, same_text = ro == rn, do == dn
         nrow += not same_row
         ntext += not same_text
-        tag = "same" if same_row and same_text else "DIFF"
-        print(f"{tag} {name}\n     old {ro} | {no} | {do}\n     new {rn} | {nn} | {dn}")
+        if same_row and same_text:   # one line for an identical kernel, both sides for one that differs
+            print(f"same {name} {ro} | {no} | {do}")
+        else:
+            print(f"DIFF {name}\n     old {ro} | {no} | {do}\n     new {rn} | {nn} | {dn}")
     print(f"common {len(set(old) & set(new))}: resource rows differ in {nrow}, instruction text differs in {ntext}")
 
 

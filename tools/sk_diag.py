@@ -1,8 +1,7 @@
 """Stream-K diagnosis on the micro-batch shapes that leave the 256 CUs idle
 (75-tile encoder launches, the decoder's N = 512 dgrads): per-launch time with
 MAECLIP_GEMM_SK = 0 (data-parallel) / 1 (forced) / auto, for the library
-MAECLIP_LIB points at (diagnostic builds: -DSKX_NO_REDUCE, -DSKX_NO_PUBLISH,
--DGEMM4_STAMPS). With a GEMM4_STAMPS build and STAMPS=1 it also prints, per
+MAECLIP_LIB points at (diagnostic build: -DGEMM4_STAMPS). With a GEMM4_STAMPS build and STAMPS=1 it also prints, per
 job slot, the median cycles of: DMA wait, K loop, fix-up + epilogue.
 python tools/sk_diag.py [label]"""
 import ctypes
