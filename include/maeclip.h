@@ -774,6 +774,68 @@ typedef struct {
 } maeclip_mix_targets_args;
 int32_t maeclip_mix_targets(const maeclip_mix_targets_args* args, void* stream);
 
+/* Stochastic depth (timm DropPath(p, scale_by_keep=True)) on a residual branch
+ * of the pre-LN blocks (droppath.hip): x <- x + s_b branch(x), one s per sample
+ * b and branch key k, drawn from the device step like the crop and mix draws,
+ * so a replayed graph draws new masks every step and a resumed run continues
+ * the sequence:
+ *   step_seed = seed + (*step_ptr) * MAECLIP_STEP_MULT         (seed if NULL)
+ *   u(b, k)   = (mc_hash4(step_seed, sample_offset + b, k, MAECLIP_DROPPATH_FIELD) >> 8) * 2^-24
+ *               (a 24-bit integer times 2^-24: exact in fp32)
+ *   keep(b,k) = u(b, k) >= p                                   (fp32 compare)
+ *   s(b, k)   = keep ? 1.0f / (1.0f - p) : 0.0f                (one IEEE fp32 division, on the host)
+ * k = 2 * block + branch, block the index in the WHOLE encoder, branch 0 =
+ * attention, 1 = MLP. The field is 32; the crop draw uses 0 .. 4 and the mix
+ * draw 16 .. 23, so at equal seeds the three are independent. sample_offset =
+ * the index of the call's first sample in the global batch (rank * B + the
+ * micro-batch's first sample), so ranks and micro-batches draw what one
+ * whole-batch launch would. Nothing is stored: each kernel re-forms s for the
+ * rows it owns (row r belongs to sample r / n).
+ *
+ * maeclip_droppath_fwd: out[r, :] = fl32(resid[r, :] + fl32(s branch[r, :])), fp32
+ * [M][D] with row strides ld_*; two roundings, no fused multiply-add, so torch's
+ * resid + s * branch is bit-exact. out == branch (same stride) is allowed: in
+ * place; any other overlap of out with branch or resid is an argument error.
+ * Rows of a dropped sample copy resid and do not read branch.
+ * maeclip_droppath_bwd: gs[r, :] = fl32(s g[r, :]) stored in gs_dtype (MAECLIP_F32:
+ * the product; MAECLIP_BF16: rounded to nearest even), g fp32; gs may not
+ * overlap g. partial f32 [maeclip_droppath_partial_rows(M)][D] (dense) gets the
+ * column sums of the fp32 products of each group of 64 consecutive rows, summed
+ * in a fixed order without atomics: reduce with maeclip_colsum_reduce (the
+ * branch's bias gradient). Groups depend on the row index alone, so launches on
+ * row ranges that start at multiples of 64 fill the same partial rows one
+ * whole launch would. Rows of a dropped sample write zeros and do not read g.
+ * Both: one launch, 16-byte accesses (8-byte for bf16 gs): D % 4 == 0, strides
+ * multiples of 4, fp32 pointers 16-byte and bf16 gs 8-byte aligned; 0 <= p < 1,
+ * n >= 1, M % n == 0, k >= 0; maeclip_droppath_bwd D <= 2048.
+ * maeclip_droppath_scales_host evaluates s on the CPU (nothing touches a
+ * device): scales [nk][B] for keys[0 .. nk), host_step a HOST pointer or NULL. */
+#define MAECLIP_DROPPATH_FIELD 32
+typedef struct {
+  const float* resid; /* fwd */
+  int64_t ld_resid;
+  const float* branch; /* fwd */
+  int64_t ld_branch;
+  float* out; /* fwd */
+  int64_t ld_out;
+  const float* g; /* bwd */
+  int64_t ld_g;
+  void* gs; /* bwd */
+  int64_t ld_gs;
+  int32_t gs_dtype;
+  float* partial; /* bwd */
+  int64_t M, D, n;
+  float p;
+  int32_t k;
+  uint64_t seed, sample_offset;
+  const int64_t* step_ptr;
+} maeclip_droppath_args;
+int32_t maeclip_droppath_fwd(const maeclip_droppath_args* args, void* stream);
+int32_t maeclip_droppath_bwd(const maeclip_droppath_args* args, void* stream);
+int64_t maeclip_droppath_partial_rows(int64_t M);
+int32_t maeclip_droppath_scales_host(float* scales, int64_t B, const int32_t* keys, int32_t nk, float p, uint64_t seed,
+                                     uint64_t sample_offset, const int64_t* host_step);
+
 /* Retrieval (inference.py:40-45). l2_normalize replaces F.normalize(x, p=2,
  * dim=-1): y = x / max(||x||_2, eps), fp32 [M][P] rows (strides ldx / ldy).
  * topk_rows replaces torch.topk(dot_similarity, k) row-wise: s fp32 [Q][N]

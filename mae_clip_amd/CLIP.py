@@ -158,16 +158,21 @@ class CLIPModel(nn.Module):
         cache = self._weight_cache()
         cache.refresh(dtype)
         mae = self.mae_decoder is not None
+        snap = self.step_snaps[self.step % 8:self.step % 8 + 1] if self.training else None
+        # drop-path of the image encoder (config.drop_path_rate > 0; on the visible tokens under MAE): the seed
+        # is the same on every rank, the sample offset tells the ranks apart. The MAE decoder and the text tower
+        # have none (HF ViTMAE / DistilBERT)
+        dp = dict(dp_seed=(self.dropout_seed * 1000003 + 43) & 0x7FFFFFFFFFFFFFFF, step_ptr=sc, bwd_step_ptr=snap,
+                  sample_offset=rank * B)
         if mae:
             ids_shuffle, ids_restore, mask, keep = self.masking(B, rank * B, img.device)
-            tokens = vit.forward_tokens(img, dtype, cache, ids_shuffle, ids_restore, keep, world=world)
+            tokens = vit.forward_tokens(img, dtype, cache, ids_shuffle, ids_restore, keep, world=world, **dp)
             dec = self.mae_decoder
             feat, latent = Fn.EncoderHeadFn.apply(tokens, dtype, vit.fc_norm.weight, vit.fc_norm.bias,
                                                   dec.mae_norm.weight, dec.mae_norm.bias)
         else:
-            tokens = vit.forward_tokens(img, dtype, cache, world=world)
+            tokens = vit.forward_tokens(img, dtype, cache, world=world, **dp)
             feat = Fn.EncoderHeadFn.apply(tokens, dtype, vit.fc_norm.weight, vit.fc_norm.bias, None, None)
-        snap = self.step_snaps[self.step % 8:self.step % 8 + 1] if self.training else None
         if use_side:
             main.wait_stream(side)
             text_features.record_stream(main)

@@ -191,6 +191,13 @@ class MixTargetsArgs(C.Structure):
                 ("B", c_i64), ("C", c_i64)]
 
 
+class DropPathArgs(C.Structure):
+    _fields_ = [("resid", c_vp), ("ld_resid", c_i64), ("branch", c_vp), ("ld_branch", c_i64), ("out", c_vp),
+                ("ld_out", c_i64), ("g", c_vp), ("ld_g", c_i64), ("gs", c_vp), ("ld_gs", c_i64), ("gs_dtype", c_i32),
+                ("partial", c_vp), ("M", c_i64), ("D", c_i64), ("n", c_i64), ("p", c_f32), ("k", c_i32),
+                ("seed", c_u64), ("sample_offset", c_u64), ("step_ptr", c_vp)]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "maeclip_abi_version": (c_i32, []),
@@ -222,6 +229,10 @@ _SIGS = {
     "maeclip_mix_params_host": (c_i32, [C.POINTER(MixParamsArgs)]),
     "maeclip_mix_images": (c_i32, [C.POINTER(MixImagesArgs), c_vp]),
     "maeclip_mix_targets": (c_i32, [C.POINTER(MixTargetsArgs), c_vp]),
+    "maeclip_droppath_fwd": (c_i32, [C.POINTER(DropPathArgs), c_vp]),
+    "maeclip_droppath_bwd": (c_i32, [C.POINTER(DropPathArgs), c_vp]),
+    "maeclip_droppath_partial_rows": (c_i64, [c_i64]),
+    "maeclip_droppath_scales_host": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_f32, c_u64, c_u64, c_vp]),
     "maeclip_l2_normalize": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_f32, c_vp]),
     "maeclip_topk_rows": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "maeclip_sim_topk_splits": (c_i32, [c_i64, c_i64, c_i64, c_i32, c_i32]),

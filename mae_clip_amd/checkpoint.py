@@ -26,6 +26,8 @@ For resuming a run this module adds what the bare state_dict cannot carry:
   * the model's training step, which keys the MAE mask noise and every dropout
     mask (CLIPModel.step / the device step_counter), so a resumed run draws
     exactly the masks the uninterrupted run would have drawn.
+Drop-path (config.drop_path_rate) needs no state of its own: its per-sample
+masks are a function of the seed and the step counter restored above.
 Files are plain tensors and ints: `load_checkpoint` reads them with
 torch.load(weights_only=True) -- nothing in a checkpoint is executed.
 """

@@ -23,8 +23,9 @@ batch["label"] when present.
 Mixup / CutMix are data.MixAugment (a CapturedStep transform that writes
 batch["target"]; label_smoothing here then gives timm's smoothed mix targets),
 layer-wise learning-rate decay is optim.layer_decay_param_groups (DESIGN.md
-Round 16). Not here: drop-path, MAE's BatchNorm1d in front of the probe head
-and LARS.
+Round 16), drop-path is ClassifierModel(drop_path_rate=...) / config.drop_path_rate
+(fine-tuning only). Not here: MAE's BatchNorm1d in front of
+the probe head and LARS.
 """
 from __future__ import annotations
 
@@ -39,7 +40,7 @@ from .modules import ImageEncoder, WeightCache, compute_dtype, _trunc_normal_
 
 
 class ClassifierModel(nn.Module):
-    def __init__(self, num_classes=None, trainable_encoder=None, label_smoothing=None):
+    def __init__(self, num_classes=None, trainable_encoder=None, label_smoothing=None, drop_path_rate=None):
         super().__init__()
         num_classes = CFG.num_classes if num_classes is None else int(num_classes)
         trainable_encoder = CFG.classifier_trainable_encoder if trainable_encoder is None else trainable_encoder
@@ -48,7 +49,15 @@ class ClassifierModel(nn.Module):
             raise ValueError(f"num_classes must be >= 1, got {num_classes}")
         if not 0.0 <= label_smoothing < 1.0:
             raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing}")
-        self.image_encoder = ImageEncoder(trainable=bool(trainable_encoder))
+        # stochastic depth regularises a trained encoder: a frozen one (linear probe) has none.
+        # config.drop_path_rate is a setting of the run and is ignored here for a probe; asking
+        # this model for it (the argument) is a mistake and raises
+        if drop_path_rate is not None and float(drop_path_rate) > 0 and not trainable_encoder:
+            raise ValueError("drop_path_rate > 0 needs trainable_encoder=True (fine-tuning); the linear probe's "
+                             "encoder is frozen")
+        self.image_encoder = ImageEncoder(trainable=bool(trainable_encoder),
+                                          drop_path_rate=drop_path_rate if trainable_encoder else 0.0)
+        self.drop_path_seed = (CFG.dropout_seed * 1000003 + 43) & 0x7FFFFFFFFFFFFFFF
         self.head = nn.Linear(self.image_encoder.model.embed_dim, num_classes)
         _trunc_normal_(self.head.weight, std=CFG.head_init_std)
         nn.init.zeros_(self.head.bias)
@@ -99,14 +108,17 @@ class ClassifierModel(nn.Module):
         pad[1][:C].copy_(b.detach())
         return Fn.HeadSpec(C=C, w_pad=pad[0], b_pad=pad[1])
 
-    def _padded_logits(self, img, world=1):
-        """[B, Cpad] fp32 logits (columns >= num_classes are padding)."""
+    def _padded_logits(self, img, world=1, rank=0, snap=None):
+        """[B, Cpad] fp32 logits (columns >= num_classes are padding). snap: the
+        step snapshot slot of a training forward (drop-path's backward reads it)."""
         Mo._require_device(img, "image batch")
         dtype = compute_dtype(self.precision)
         vit = self.image_encoder.model
         cache = self._weight_cache()
         cache.refresh(dtype)
-        tokens = vit.forward_tokens(img, dtype, cache, world=world)
+        # the drop-path seed is the same on every rank: the sample offset tells the ranks apart
+        tokens = vit.forward_tokens(img, dtype, cache, world=world, dp_seed=self.drop_path_seed,
+                                    step_ptr=self.step_counter, bwd_step_ptr=snap, sample_offset=rank * img.shape[0])
         feat = Fn.EncoderHeadFn.apply(tokens, dtype, vit.fc_norm.weight, vit.fc_norm.bias, None, None)
         return Fn.ClassifierHeadFn.apply(feat, self._head_spec(), self.head.weight, self.head.bias)
 
@@ -126,9 +138,10 @@ class ClassifierModel(nn.Module):
         Mo._require_device(img, "image batch")
         sc = self.step_counter
         Mo._require_device(sc, "ClassifierModel.step_counter (call .to(device))")
-        world, _ = self._world()
+        world, rank = self._world()
         Fn.set_grad_arena(self.grad_arena if torch.is_grad_enabled() else None)
-        logits = self._padded_logits(img, world)
+        snap = self.step_snaps[self.step % 8:self.step % 8 + 1] if self.training else None
+        logits = self._padded_logits(img, world, rank, snap)
         targets = batch.get("target")
         labels = None
         if targets is None:
@@ -145,7 +158,7 @@ class ClassifierModel(nn.Module):
         loss = Fn.SoftmaxXentFn.apply(logits, labels, targets, spec)
         self.last_losses = {"xent": loss.detach()}
         if self.training:
-            K.counter_add_snap(sc, self.step_snaps[self.step % 8:self.step % 8 + 1], 1)
+            K.counter_add_snap(sc, snap, 1)
             self.step += 1
         return loss
 

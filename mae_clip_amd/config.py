@@ -99,6 +99,12 @@ num_classes = 1000
 label_smoothing = 0.0              # F.cross_entropy's label_smoothing (MAE fine-tuning uses 0.1)
 classifier_trainable_encoder = False   # False: linear probe (frozen encoder, only the head trains); True: fine-tuning
 head_init_std = 0.02               # head.weight trunc-normal(std), head.bias zero (timm / MAE)
+# ---- stochastic depth of the image encoder (timm drop_path_rate), training mode only: block i drops each residual
+# branch of a sample with probability linspace(0, rate, depth)[i]. 0: off (today's launches). MAE fine-tunes ViT-B
+# with 0.1, ViT-L / ViT-H with 0.2 / 0.3. Read by VisionTransformer; not available with precision "fp8".
+# ClassifierModel applies it when its encoder trains (fine-tuning) and ignores it for the linear probe, whose
+# frozen encoder has nothing to regularise; only an explicit ClassifierModel(drop_path_rate > 0) on a probe raises.
+drop_path_rate = 0.0
 # ---- Mixup / CutMix on the device (data.MixAugment); read by data.mix_augment_from_config() only. Both alphas 0:
 # off (the default). MAE's / timm's fine-tuning recipe: mixup_alpha 0.8, cutmix_alpha 1.0, label_smoothing 0.1.
 mixup_alpha = 0.0                  # Beta(alpha, alpha) of the mixup weight; 0: no mixup

@@ -142,6 +142,44 @@ class StackSpec:
     side: bool = True               # weight gradients on the side stream (when not grouped)
     grouped_wgrad: bool = True      # one grouped launch for all weight gradients of the stack
     w8: list = None                 # fp8 mode: per block ((W, W^T) fp8 operands) x (qkv, proj, fc1, fc2)
+    # drop-path (timm DropPath, scale_by_keep) on both residual branches: all off by default
+    drop_path: tuple = None         # per block: the drop rate (None / 0: today's launches); not with w8
+                                    # (modules.run_stack refuses the pair before anything is launched)
+    dp_seed: int = 0
+    step_ptr: torch.Tensor = None   # device step counter keying the masks (None: step 0)
+    bwd_step_ptr: torch.Tensor = None   # the same step's value as the backward will find it (snapshot slot)
+    sample_offset: int = 0          # index of the stack's first sample in the global batch (rank * B)
+    block0: int = 0                 # index of the stack's first block in the whole encoder
+
+
+@dataclass
+class DropPath:
+    """The draw of one block's two branches for the rows of one launch chain:
+    branch key k = 2 * block + (0: attention, 1: MLP) (include/maeclip.h)"""
+    p: float
+    block: int
+    seed: int
+    sample_offset: int
+    step_ptr: torch.Tensor
+
+    def kw(self, branch):
+        return dict(p=self.p, k=2 * self.block + branch, seed=self.seed, sample_offset=self.sample_offset,
+                    step_ptr=self.step_ptr)
+
+
+def drop_rate(spec, i):
+    """drop rate of block i of the stack (0: the block does not drop)"""
+    return float(spec.drop_path[i]) if spec.drop_path else 0.0
+
+
+def _drop(spec, i, step_ptr, b0=0):
+    """DropPath of block i of the stack for the rows starting at its sample b0
+    (None: the block does not drop); step_ptr: the forward's counter, or the
+    value the backward reads (step_snapshot)"""
+    p = drop_rate(spec, i)
+    if p <= 0.0:
+        return None
+    return DropPath(p, spec.block0 + i, spec.dp_seed, spec.sample_offset + b0, step_ptr)
 
 
 def _quant8(x, fmt, colsum):
@@ -309,10 +347,12 @@ def _noop(*a):
     pass
 
 
-def block_forward(spec, w, p, f8, x, Bs, d={}, tick=_noop):
+def block_forward(spec, w, p, f8, x, Bs, d={}, tick=_noop, dp=None):
     """The 7 forward launches of one pre-LN block (LN, qkv, attention,
     proj + residual, LN, fc1 + GELU', fc2 + residual) on the rows x [Bs * n, D]
-    of Bs whole samples, on the current stream. w: the block's (qkv, proj, fc1,
+    of Bs whole samples, on the current stream. dp (DropPath, a dropping block):
+    9 launches -- proj and fc2 write bias + product alone and a drop-path launch
+    each adds the scaled branch to the residual in place. w: the block's (qkv, proj, fc1,
     fc2) weights in spec.dtype, p: its PER_BLOCK parameters, f8: _f8(spec, i).
     d: destinations by name (h1 m1 r1 qkv o lse x1 h2 m2 r2 dgelu a x2), e.g.
     row slices of whole-batch buffers; an output without one is a new tensor.
@@ -333,8 +373,13 @@ def block_forward(spec, w, p, f8, x, Bs, d={}, tick=_noop):
     o8 = _attn_q8(f8[1], M, D, K.FP8_E4M3, dev, False)   # the proj GEMM's fp8 operand
     o, lse = K.attn_fwd(qkv, Bs, n, H, hd, hd ** -0.5, q8=o8, o_out=d.get("o"), lse_out=d.get("lse"))
     tick()
-    x1 = _fwd(o, wproj, f8[1], xq=o8, bias=bproj, out_dtype=torch.float32, epilogue=K.EPI_RESID, resid=x,
-              out=d.get("x1"))
+    if dp is None:
+        x1 = _fwd(o, wproj, f8[1], xq=o8, bias=bproj, out_dtype=torch.float32, epilogue=K.EPI_RESID, resid=x,
+                  out=d.get("x1"))
+    else:
+        x1 = _fwd(o, wproj, f8[1], xq=o8, bias=bproj, out_dtype=torch.float32, out=d.get("x1"))
+        tick()
+        K.droppath_fwd(x, x1, n, **dp.kw(0))
     del o8
     tick()
     q2 = _q8(f8[2], M, D, K.FP8_E4M3, dev)
@@ -348,11 +393,17 @@ def block_forward(spec, w, p, f8, x, Bs, d={}, tick=_noop):
     a = _fwd(h2, w1, f8[2], xq=q2, q8=a8, bias=b1, epilogue=K.EPI_GELU_D, aux_out=dgelu, out=d.get("a"))
     del q2
     tick()
-    x2 = _fwd(a, w2, f8[3], xq=a8, bias=b2, out_dtype=torch.float32, epilogue=K.EPI_RESID, resid=x1, out=d.get("x2"))
+    if dp is None:
+        x2 = _fwd(a, w2, f8[3], xq=a8, bias=b2, out_dtype=torch.float32, epilogue=K.EPI_RESID, resid=x1,
+                  out=d.get("x2"))
+    else:
+        x2 = _fwd(a, w2, f8[3], xq=a8, bias=b2, out_dtype=torch.float32, out=d.get("x2"))
+        tick()
+        K.droppath_fwd(x1, x2, n, **dp.kw(1))
     return dict(x=x, h1=h1, m1=m1, r1=r1, qkv=qkv, o=o, lse=lse, x1=x1, h2=h2, m2=m2, r2=r2, dgelu=dgelu, a=a), x2
 
 
-def block_backward(spec, w, p, f8, f8n, t, Bs, d={}, after=_noop):
+def block_backward(spec, w, p, f8, f8n, t, Bs, d={}, after=_noop, dp=None, below_drops=False):
     """The 7 backward launches of one block (fc2 dgrad x GELU', fc1 dgrad, LN,
     proj dgrad, attention, qkv dgrad, LN) on the rows of Bs whole samples, on
     the current stream. t: the block's tensors of these rows by name -- the
@@ -362,7 +413,15 @@ def block_backward(spec, w, p, f8, f8n, t, Bs, d={}, after=_noop):
     and pc1 are the block below's g, gT, gq and column partials. f8n: the fc2
     operand of the block below (its dgrad reads dxT). d: destinations by name;
     after(k) is called between launch k and launch k + 1 (the gradients _GRADS
-    lists for launch k can be booked from t there)."""
+    lists for launch k can be booked from t there).
+    dp (DropPath, a dropping block; its step_ptr holds the forward's step): 9
+    launches. The branch gradients are s * g and s * dx1: a drop-path launch in
+    front of the fc2 dgrad replaces gT and cpart from above by the scaled copy
+    of g and its column partials, and one behind the norm2 backward (part of
+    launch 2 for after()) makes dx1T and pc2 from dx1, so _GRADS books the same
+    12 gradients from the scaled tensors; the residual path (dres of both
+    LayerNorm backwards) stays unscaled. below_drops: the block below makes its
+    own fc2 operand, so dxT and pc1 are not produced (None)."""
     wqkv, wproj, w1, w2 = w
     n1w, n2w = p[0], p[6]
     n, D, H = spec.n, spec.D, spec.H
@@ -371,6 +430,9 @@ def block_backward(spec, w, p, f8, f8n, t, Bs, d={}, after=_noop):
     bf = spec.dtype == torch.bfloat16
     M, F, dev = Bs * n, w1.shape[0], t["g"].device
     gq = t.pop("gq")
+    T = spec.dtype
+    if dp is not None:
+        t["gT"], t["cpart"] = K.droppath_bwd(t["g"], n, dtype=T, out=d.get("gT"), partial=d.get("cpart"), **dp.kw(1))
     # mlp.fc2 (+ GELU backward fused into the dgrad epilogue: dA = (dy W2) * gelu'(h))
     t["dA_part"] = _dst(d, "dA_part", (K.gemm_colsum_rows(M), F), torch.float32, dev)
     dA8 = _b8(f8[2], M, F, _gfmt(), dev)   # fc1's dgrad operand (fp8 mode)
@@ -385,10 +447,15 @@ def block_backward(spec, w, p, f8, f8n, t, Bs, d={}, after=_noop):
     del t["dA"]
     # norm2 (+ residual gradient)
     q1 = _q8(f8[1], M, D, _gfmt(), dev)
-    dx1, dx1T, t["pg2"], t["pb2"], t["pc2"] = K.ln_bwd(
-        dh2, t["x1"], t["m2"], t["r2"], n2w, dres=t["g"], want_bf16=bf, want_colsum=True, q8=q1, dx_out=d.get("dx1"),
-        dxb_out=d.get("dx1T"), pg_out=d.get("pg2"), pb_out=d.get("pb2"), pc_out=d.get("pc2"))
-    t["dx1T"] = dx1T if bf else dx1
+    if dp is None:
+        dx1, dx1T, t["pg2"], t["pb2"], t["pc2"] = K.ln_bwd(
+            dh2, t["x1"], t["m2"], t["r2"], n2w, dres=t["g"], want_bf16=bf, want_colsum=True, q8=q1,
+            dx_out=d.get("dx1"), dxb_out=d.get("dx1T"), pg_out=d.get("pg2"), pb_out=d.get("pb2"), pc_out=d.get("pc2"))
+        t["dx1T"] = dx1T if bf else dx1
+    else:
+        dx1, _, t["pg2"], t["pb2"], _ = K.ln_bwd(dh2, t["x1"], t["m2"], t["r2"], n2w, dres=t["g"], dx_out=d.get("dx1"),
+                                                 pg_out=d.get("pg2"), pb_out=d.get("pb2"))
+        t["dx1T"], t["pc2"] = K.droppath_bwd(dx1, n, dtype=T, out=d.get("dx1T"), partial=d.get("pc2"), **dp.kw(0))
     after(2)
     # attn.proj
     dO = _dgrad(t["dx1T"], wproj, f8[1], dyq=q1, out=d.get("dO"))
@@ -408,9 +475,10 @@ def block_backward(spec, w, p, f8, f8n, t, Bs, d={}, after=_noop):
     # quantised here when it is fp8
     t["gq"] = _q8(f8n, M, D, _gfmt(), dev)
     t["dx"], dxT, t["pg1"], t["pb1"], t["pc1"] = K.ln_bwd(
-        dh1, t["x"], t["m1"], t["r1"], n1w, dres=dx1, want_bf16=bf, want_colsum=True, q8=t["gq"], dx_out=d.get("dx"),
-        dxb_out=d.get("dxT"), pg_out=d.get("pg1"), pb_out=d.get("pb1"), pc_out=d.get("pc1"))
-    t["dxT"] = dxT if bf else t["dx"]
+        dh1, t["x"], t["m1"], t["r1"], n1w, dres=dx1, want_bf16=bf and not below_drops, want_colsum=not below_drops,
+        q8=t["gq"], dx_out=d.get("dx"), dxb_out=d.get("dxT"), pg_out=d.get("pg1"), pb_out=d.get("pb1"),
+        pc_out=d.get("pc1"))
+    t["dxT"] = None if below_drops else (dxT if bf else t["dx"])
 
 
 # The 12 parameter gradients of a block in booking order: (the backward launch
@@ -450,14 +518,15 @@ class TransformerStackFn(torch.autograd.Function):
             saved, xi = TransformerStackFn._forward_microbatches(spec, blocks, xi, S)
         else:
             saved = []
-            for w, p, f8 in blocks:
-                t, xi = block_forward(spec, w, p, f8, xi, B)
+            for i, (w, p, f8) in enumerate(blocks):
+                t, xi = block_forward(spec, w, p, f8, xi, B, dp=_drop(spec, i, spec.step_ptr))
                 saved.append(t)
         ctx.saved = saved
         ctx.spec = spec
         ctx.params = params
         ctx.arena = _arena()
         ctx.S = S
+        ctx.step_snap = step_snapshot(spec, any(drop_rate(spec, i) > 0 for i in range(len(blocks))))
         return xi.view(B, n, D)
 
     @staticmethod
@@ -483,7 +552,8 @@ class TransformerStackFn(torch.autograd.Function):
             for mi, rs, bs in mb.each():
                 d = {k: v[bs if k == "lse" else rs] for k, v in saved[i].items() if v is not None}
                 d["x2"] = outs[i][rs]
-                _, xin[mi] = block_forward(spec, w, p, f8, xin[mi], mb.Bs, d, mb.tick)
+                _, xin[mi] = block_forward(spec, w, p, f8, xin[mi], mb.Bs, d, mb.tick,
+                                           dp=_drop(spec, i, spec.step_ptr, bs.start))
         mb.join()
         for i in range(len(blocks)):
             saved[i]["x"] = xi if i == 0 else outs[i - 1]
@@ -504,12 +574,18 @@ class TransformerStackFn(torch.autograd.Function):
         g = gy.reshape(M, D)
         if not g.is_contiguous():
             g = g.contiguous()
-        gT = torch.empty((M, D), device=dev, dtype=torch.bfloat16) if bf else None
-        # fp8 copy of gT for the top fc2 dgrad: made with gT here (fp8 mode), then
-        # by the LayerNorm backward that produces each next gT
-        gq = _q8(blocks[-1][2][3], M, D, _gfmt(), dev)
-        cpart = K.rows_colsum(g, out_bf16=gT, q8=gq)
-        up = dict(g=g, gT=gT if bf else g, gq=gq, cpart=cpart)
+        # a dropping block makes its fc2 operand and bias partials from g itself
+        # (block_backward): the copy from above is then not produced
+        drops = [drop_rate(spec, i) > 0 for i in range(L)]
+        gT = gq = cpart = None
+        if not drops[-1]:
+            gT = torch.empty((M, D), device=dev, dtype=torch.bfloat16) if bf else None
+            # fp8 copy of gT for the top fc2 dgrad: made with gT here (fp8 mode), then
+            # by the LayerNorm backward that produces each next gT
+            gq = _q8(blocks[-1][2][3], M, D, _gfmt(), dev)
+            cpart = K.rows_colsum(g, out_bf16=gT, q8=gq)
+            gT = gT if bf else g
+        up = dict(g=g, gT=gT, gq=gq, cpart=cpart)
         del g, gT, gq, cpart
         if S > 1:
             g = TransformerStackFn._backward_microbatches(ctx, blocks, up, rb, wq, grads)
@@ -518,7 +594,8 @@ class TransformerStackFn(torch.autograd.Function):
                 w, p, f8, f8n = blocks[i]
                 t = dict(ctx.saved[i], **up)
                 up = None
-                block_backward(spec, w, p, f8, f8n, t, B, after=lambda k: _book(grads[i], rb, wq, ctx.arena, p, t, k))
+                block_backward(spec, w, p, f8, f8n, t, B, after=lambda k: _book(grads[i], rb, wq, ctx.arena, p, t, k),
+                               dp=_drop(spec, i, ctx.step_snap), below_drops=i > 0 and drops[i - 1])
                 _book(grads[i], rb, wq, ctx.arena, p, t, 6)
                 ctx.saved[i] = None
                 up = dict(g=t["dx"], gT=t["dxT"], gq=t["gq"], cpart=t["pc1"])
@@ -540,18 +617,25 @@ class TransformerStackFn(torch.autograd.Function):
         GC = K.gemm_colsum_rows(M)              # GEMM column-sum partial rows (64-row groups)
         # whole-batch gradient buffers of every block, written per micro-batch
         bufs = []
-        for (_, _, w1, _), _, _, _ in blocks:
+        drops = [drop_rate(spec, i) > 0 for i in range(len(blocks))]
+        GD = K.droppath_partial_rows(M // S) if any(drops) else 0   # drop-path partial rows per micro-batch
+        for i, ((_, _, w1, _), _, _, _) in enumerate(blocks):
             F = w1.shape[0]
-            bufs.append(dict(dA=e((M, F)), dA_part=e((GC, F), f32), dh2=e((M, D)), dx1=e((M, D), f32),
-                             dx1T=e((M, D)), pg2=e((S * G, D), f32), pb2=e((S * G, D), f32),
-                             pc2=e((S * G, D), f32), dO=e((M, D)), dqkv=e((M, 3 * D)), qpart=e((B, 3 * D), f32),
-                             dh1=e((M, D)), dx=e((M, D), f32), dxT=e((M, D)), pg1=e((S * G, D), f32),
-                             pb1=e((S * G, D), f32), pc1=e((S * G, D), f32)))
+            b = dict(dA=e((M, F)), dA_part=e((GC, F), f32), dh2=e((M, D)), dx1=e((M, D), f32),
+                     dx1T=e((M, D)), pg2=e((S * G, D), f32), pb2=e((S * G, D), f32),
+                     pc2=e((S * G, D), f32), dO=e((M, D)), dqkv=e((M, 3 * D)), qpart=e((B, 3 * D), f32),
+                     dh1=e((M, D)), dx=e((M, D), f32), dxT=e((M, D)), pg1=e((S * G, D), f32),
+                     pb1=e((S * G, D), f32), pc1=e((S * G, D), f32))
+            if drops[i]:    # its own scaled copies of g and dx1, with their partials
+                b.update(gT=e((M, D)), cpart=e((S * GD, D), f32), pc2=e((S * GD, D), f32))
+            if i > 0 and drops[i - 1]:
+                del b["dxT"], b["pc1"]
+            bufs.append(b)
         mb.fork()
         # per micro-batch: (f32 residual gradient, its bf16 copy, the copy's fp8
         # rows from the LayerNorm backward that made it -- fp8 mode)
         g, gT, gq = up["g"], up["gT"], up["gq"]
-        ups = [dict(g=g[r0:r1], gT=gT[r0:r1],
+        ups = [dict(g=g[r0:r1], gT=None if gT is None else gT[r0:r1],
                     gq=None if gq is None else K.Fp8Rows(gq.q[r0:r1], gq.s[r0:r1], gq.fmt)) for r0, r1 in mb.rows]
         for i in reversed(range(len(blocks))):
             w, p, f8, f8n = blocks[i]
@@ -560,16 +644,20 @@ class TransformerStackFn(torch.autograd.Function):
                 # attention's bias partials), its 64-row groups, its LayerNorm partial rows
                 sel = dict.fromkeys(("pg2", "pb2", "pc2", "pg1", "pb1", "pc1"), slice(mi * G, (mi + 1) * G))
                 sel.update(lse=bs, qpart=bs, dA_part=slice(rs.start // 64, rs.stop // 64))
+                if drops[i]:
+                    sel.update(dict.fromkeys(("cpart", "pc2"), slice(mi * GD, (mi + 1) * GD)))
                 t = {k: v[sel.get(k, rs)] for k, v in saved[i].items()}
                 t.update(ups[mi])
                 d = {k: v[sel.get(k, rs)] for k, v in bufs[i].items()}
-                block_backward(spec, w, p, f8, f8n, t, mb.Bs, d, after=lambda k: mb.tick())
+                block_backward(spec, w, p, f8, f8n, t, mb.Bs, d, after=lambda k: mb.tick(),
+                               dp=_drop(spec, i, ctx.step_snap, bs.start), below_drops=i > 0 and drops[i - 1])
                 ups[mi] = dict(g=t["dx"], gT=t["dxT"], gq=t["gq"])
         mb.join()
         gT, cpart = up["gT"], up["cpart"]
         for i in reversed(range(len(blocks))):
-            _book(grads[i], rb, wq, ctx.arena, blocks[i][1], dict(saved[i], **bufs[i], gT=gT, cpart=cpart))
-            gT, cpart = bufs[i]["dxT"], bufs[i]["pc1"]
+            # (a dropping block's own gT / cpart in bufs[i] take the place of those from above)
+            _book(grads[i], rb, wq, ctx.arena, blocks[i][1], {**saved[i], "gT": gT, "cpart": cpart, **bufs[i]})
+            gT, cpart = bufs[i].get("dxT"), bufs[i].get("pc1")
         return bufs[0]["dx"]
 
 

@@ -525,6 +525,71 @@ def dropout(x, p, seed, out=None, step_ptr=None):
     return out
 
 
+# ------------------------------------------------------------ drop-path
+DROPPATH_MAX_D = 2048    # widest row of maeclip_droppath_bwd (include/maeclip.h)
+
+
+def _droppath_args(M, D, n, p, k, seed, sample_offset, step_ptr, **fields):
+    return L.DropPathArgs(M=M, D=D, n=int(n), p=float(p), k=int(k), seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
+                          sample_offset=int(sample_offset), step_ptr=_ptr(step_ptr), **fields)
+
+
+def droppath_fwd(resid, branch, n, p, k, seed=0, sample_offset=0, step_ptr=None, out=None):
+    """out = resid + s * branch, s per sample (row r: sample r // n) and branch
+    key k: 1 / (1 - p) when kept, 0 when dropped (include/maeclip.h "Stochastic
+    depth"). f32 [M, D] rows; out None: in place on branch. step_ptr: device
+    int64 step counter (None: step 0)."""
+    out = branch if out is None else out
+    _dev(resid, branch, out, step_ptr)
+    M, D = branch.shape
+    for t in (resid, branch, out):
+        if t.dtype != torch.float32 or t.shape != (M, D) or t.stride(1) != 1:
+            raise ValueError("droppath_fwd: resid, branch and out must be f32 [M, D] rows")
+    a = _droppath_args(M, D, n, p, k, seed, sample_offset, step_ptr, resid=resid.data_ptr(), ld_resid=resid.stride(0),
+                       branch=branch.data_ptr(), ld_branch=branch.stride(0), out=out.data_ptr(), ld_out=out.stride(0))
+    _call("maeclip_droppath_fwd", C.byref(a), _stream())
+    return out
+
+
+def droppath_partial_rows(M: int) -> int:
+    return int(L.lib().maeclip_droppath_partial_rows(M))
+
+
+def droppath_bwd(g, n, p, k, dtype, seed=0, sample_offset=0, step_ptr=None, out=None, partial=None):
+    """(gs = s * g in `dtype` (f32: the product; bf16: rounded to nearest even),
+    the column sums of the f32 products per 64-row group, f32
+    [droppath_partial_rows(M), D]: the branch's bias gradient after a column
+    reduction). g f32 [M, D] rows; s and step_ptr as droppath_fwd (step_ptr must
+    hold the value the forward ran with)."""
+    _dev(g, out, partial, step_ptr)
+    M, D = g.shape
+    if g.dtype != torch.float32 or g.stride(1) != 1:
+        raise ValueError("droppath_bwd: g must be f32 [M, D] rows")
+    gs = out if out is not None else torch.empty((M, D), device=g.device, dtype=dtype)
+    G = droppath_partial_rows(M)
+    part = partial if partial is not None else torch.empty((G, D), device=g.device, dtype=torch.float32)
+    if gs.shape != (M, D) or gs.dtype != dtype or gs.stride(1) != 1 or part.shape != (G, D) \
+            or part.dtype != torch.float32 or not part.is_contiguous():
+        raise ValueError("droppath_bwd: out must be [M, D] rows of `dtype`, partial dense f32 [partial rows, D]")
+    a = _droppath_args(M, D, n, p, k, seed, sample_offset, step_ptr, g=g.data_ptr(), ld_g=g.stride(0),
+                       gs=gs.data_ptr(), ld_gs=gs.stride(0), gs_dtype=_dt(gs), partial=part.data_ptr())
+    _call("maeclip_droppath_bwd", C.byref(a), _stream())
+    return gs, part
+
+
+def droppath_scales_host(B, k, p, seed=0, step=0, sample_offset=0):
+    """The scales s the drop-path kernels form at device step `step`, evaluated
+    on the CPU by the same function (no device needed). k: one branch key ->
+    CPU f32 [B]; a sequence of keys -> [len(k), B]."""
+    keys = [int(k)] if isinstance(k, int) else [int(v) for v in k]
+    out = torch.empty((len(keys), B), dtype=torch.float32)
+    karr = (C.c_int32 * max(len(keys), 1))(*keys)
+    step_v = C.c_int64(int(step))
+    _call("maeclip_droppath_scales_host", out.data_ptr(), B, C.addressof(karr), len(keys), float(p),
+          int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_offset), C.addressof(step_v))
+    return out[0] if isinstance(k, int) else out
+
+
 def embed_fwd(ids, word, pos, mask=None):
     """word + position embedding rows [B*T, D] (f32). mask (optional, int64
     [B, T] attention_mask): also returns it as the f32 key mask [B, T],

@@ -240,22 +240,41 @@ def chunk_bounds(n, chunk):
     return out
 
 
-def run_stack(blocks, x, heads, dtype, cache: WeightCache, chunk=None, fp8=True):
+def drop_path_rates(rate, depth):
+    """timm's stochastic depth decay rule: block i of `depth` drops a branch
+    with probability torch.linspace(0, rate, depth)[i] (block 0: never)."""
+    return [float(v) for v in torch.linspace(0, float(rate), int(depth))]
+
+
+def run_stack(blocks, x, heads, dtype, cache: WeightCache, chunk=None, fp8=True, drop_path=None, dp_seed=0,
+              step_ptr=None, bwd_step_ptr=None, sample_offset=0):
     """The blocks as one TransformerStackFn, or as consecutive Functions of
     `chunk` blocks: autograd accumulates a Function's parameter gradients when
     its backward returns, so under data parallelism a chunked encoder hands its
     upper blocks' gradients to the bucketed all-reduce while the backward of the
     lower blocks is still running (the all-reduce of the last stack in the
     backward is otherwise fully exposed). fp8=False keeps a stack on bf16 GEMMs
-    when the cache is in fp8 mode."""
+    when the cache is in fp8 mode. drop_path: the per-block drop rates of the
+    whole stack (None / all 0: no drop-path), drawn with dp_seed from the device
+    step step_ptr (bwd_step_ptr: its snapshot slot, as ProjectionHead) for the
+    samples sample_offset .. of the global batch (functions.StackSpec)."""
     B, n, D = x.shape
+    if drop_path is not None and not any(r > 0 for r in drop_path):
+        drop_path = None
     for c0, c1 in chunk_bounds(len(blocks), chunk):
         part = blocks[c0:c1]
+        drop = tuple(drop_path[c0:c1]) if drop_path is not None and any(r > 0 for r in drop_path[c0:c1]) else None
         wT = [tuple(cache.get(w, dtype) for w in blk.gemm_weights()) for blk in part]
         w8 = ([tuple(cache.get_fp8(w) for w in blk.gemm_weights()) for blk in part]
               if fp8 and getattr(cache, "fp8", False) and dtype == torch.bfloat16 else None)
         spec = Fn.StackSpec(B=B, n=n, D=D, H=heads, eps=part[0].norm1.eps, dtype=dtype, wT=wT,
                             side=bool(CFG.side_stream), grouped_wgrad=bool(CFG.wgrad_grouped), w8=w8)
+        if drop is not None:
+            if w8 is not None:
+                raise ValueError("drop-path is not available with precision='fp8'; use 'bf16' or 'fp32', or "
+                                 "drop_path_rate = 0")
+            spec.drop_path, spec.dp_seed, spec.block0 = drop, int(dp_seed), c0
+            spec.step_ptr, spec.bwd_step_ptr, spec.sample_offset = step_ptr, bwd_step_ptr, int(sample_offset)
         params = [p for blk in part for p in blk.stack_params()]
         x = Fn.TransformerStackFn.apply(x, spec, *params)
     return x
@@ -275,7 +294,7 @@ class VisionTransformer(nn.Module):
     """timm VisionTransformer(num_classes=0, global_pool="avg") parameter layout
     (fc_norm used, final norm Identity)."""
 
-    def __init__(self, model_name, img_size=None, depth=None):
+    def __init__(self, model_name, img_size=None, depth=None, drop_path_rate=None):
         super().__init__()
         if model_name not in VIT_SPECS:
             raise ValueError(f"unsupported image model {model_name!r}; supported: {sorted(VIT_SPECS)}")
@@ -291,6 +310,17 @@ class VisionTransformer(nn.Module):
         self.fc_norm = nn.LayerNorm(D, eps=1e-6)
         self.num_features = D
         self.precision = CFG.precision
+        # stochastic depth (timm drop_path_rate): block i drops each residual branch of a
+        # sample with probability linspace(0, rate, depth)[i], in training mode only
+        self.drop_path_rate = float(CFG.drop_path_rate if drop_path_rate is None else drop_path_rate)
+        if not 0.0 <= self.drop_path_rate < 1.0:
+            raise ValueError(f"drop_path_rate must be in [0, 1), got {self.drop_path_rate}")
+        if self.drop_path_rate > 0 and self.precision == "fp8":
+            raise ValueError("drop_path_rate > 0 is not available with precision='fp8' (the fp8 operands of the "
+                             "scaled gradients have no producer); use 'bf16' or 'fp32'")
+        if self.drop_path_rate > 0 and D > K.DROPPATH_MAX_D:
+            raise ValueError(f"drop_path_rate > 0 needs embed_dim <= {K.DROPPATH_MAX_D} (maeclip_droppath_bwd keeps a "
+                             f"row's column sums in registers), got {D}")
         _trunc_normal_(self.pos_embed)
         nn.init.normal_(self.cls_token, std=1e-6)
         for blk in self.blocks:
@@ -305,10 +335,16 @@ class VisionTransformer(nn.Module):
                 cache.register(p, p.shape)
                 cache.register_fp8(p)
 
-    def forward_tokens(self, img, dtype, cache, ids_shuffle=None, ids_restore=None, keep=None, world=1):
+    def forward_tokens(self, img, dtype, cache, ids_shuffle=None, ids_restore=None, keep=None, world=1, dp_seed=0,
+                       step_ptr=None, bwd_step_ptr=None, sample_offset=0):
         """img: the reference's fp32 NCHW batch [B,3,S,S] (dataset.py:34), or the
         decoded uint8 RGB pixels [B,S,S,3] (HWC), normalised inside the patch
-        gather (A.Normalize of dataset.py:49 fused; no fp32 image in HBM)."""
+        gather (A.Normalize of dataset.py:49 fused; no fp32 image in HBM).
+        Drop-path (drop_path_rate > 0, training mode): the masks are drawn with
+        dp_seed from the device step counter step_ptr (None: step 0 on every
+        call) for the samples sample_offset .. sample_offset + B - 1 of the
+        global batch; bwd_step_ptr: the snapshot slot the backward reads the
+        step from (None: it keeps a copy), as ProjectionHead."""
         _require_device(img, "image batch")
         img = as_model_image(img, self.patch_embed.img_size)
         pe = self.patch_embed
@@ -336,7 +372,11 @@ class VisionTransformer(nn.Module):
         # under data parallelism (world = size of the model's process group) the
         # stack is cut into chunks so upper blocks' gradients reach the all-reduce early
         chunk = (CFG.dp_encoder_chunk or None) if world > 1 else None
-        return run_stack(self.blocks, x, self.num_heads, dtype, cache, chunk=chunk)
+        drop = None
+        if self.training and self.drop_path_rate > 0:
+            drop = drop_path_rates(self.drop_path_rate, len(self.blocks))
+        return run_stack(self.blocks, x, self.num_heads, dtype, cache, chunk=chunk, drop_path=drop, dp_seed=dp_seed,
+                         step_ptr=step_ptr, bwd_step_ptr=bwd_step_ptr, sample_offset=sample_offset)
 
     def forward(self, img):
         """timm semantics: pooled + fc_norm features [B, D] (no masking)."""
@@ -354,14 +394,15 @@ class VisionTransformer(nn.Module):
 class ImageEncoder(nn.Module):
     """modules.py:8-31: encode images to a fixed size vector (timm ViT, avg pool)."""
 
-    def __init__(self, model_name=None, pretrained=None, trainable=None, img_size=None, depth=None):
+    def __init__(self, model_name=None, pretrained=None, trainable=None, img_size=None, depth=None,
+                 drop_path_rate=None):
         super().__init__()
         model_name = model_name or CFG.model_name
         pretrained = CFG.pretrained if pretrained is None else pretrained
         trainable = CFG.trainable if trainable is None else trainable
         if pretrained:
             raise RuntimeError("pretrained hub weights are unavailable offline; load a state_dict instead")
-        self.model = VisionTransformer(model_name, img_size or CFG.size, depth)
+        self.model = VisionTransformer(model_name, img_size or CFG.size, depth, drop_path_rate)
         for p in self.model.parameters():
             p.requires_grad = trainable
 
